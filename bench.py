@@ -5,11 +5,14 @@ bs=8 per GPU, bf16 MFMA with fp32 accumulate, `LARPTokenizer(bottleneck_type='vq
 
   python bench.py [--gpus N --steps K --warmup W]          (N > 1 without a launcher: spawns its own N rank processes)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
+  python bench.py --full                                   (+ roofline replays, host enqueue probe, stock-PyTorch yardstick, CPU baseline)
+  python bench.py --dump-outputs DIR                       (+ the last timed step's outputs as DIR/<name>.npy)
 
 A "step" = model(data) -> L1 reconstruction loss + 0.1*loss_q (the model-side part of
 trainers/larp_tokenizer_trainer.py:_iter_step; LPIPS/GAN are out of scope) -> backward through the HIP
 engine (-> bucketed RCCL gradient all-reduce); `--optimizer` additionally runs torch.optim.Adam in the step.
-Inputs are resident in HBM before the timed region.  Rank 0 prints ONE JSON line.
+Inputs are resident in HBM before the timed region.  Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the
+steps and prints the line; every figure that needs runs of its own (or reads committed records) is measured with --full only.
 """
 import argparse
 import json
@@ -390,6 +393,33 @@ def gan_step(vt, model, x, steps, warmup):
             "what": "tokenizer fwd+bwd + generator-side pass through the discriminator every step + discriminator update every 5th step; LPIPS off"}
 
 
+DUMP_SAMPLE = 1 << 20   # elements written of a larger output: at most ~16 arrays x 4 MB stay under the 64 MB the dump may take
+
+
+def dump_outputs(path, loss, out, model):
+    """--dump-outputs: what the last timed step handed its caller -- the loss, every tensor of the model's output dict and the parameter
+    gradients (concatenated in named_parameters() order, key 'grads') -- as path/<name>.npy, float32 (float64 for integer tensors such as
+    the token ids).  An array of more than DUMP_SAMPLE elements is written as its flattened values at DUMP_SAMPLE positions drawn by a
+    fixed seed from its size alone, so two runs or two builds with the same arguments write the same positions."""
+    import numpy as np
+    arrays = {"loss": loss}
+    arrays.update((k, v) for k, v in out.items() if torch.is_tensor(v))
+    grads = [p.grad.detach().reshape(-1).float() for p in model.parameters() if p.grad is not None]
+    if grads:
+        arrays["grads"] = torch.cat(grads)
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(t.numel()).choice(t.numel(), DUMP_SAMPLE, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        a = (t.float() if t.is_floating_point() else t.double()).cpu().numpy()
+        total += a.nbytes
+        assert total <= 64 << 20, f"--dump-outputs would write more than 64 MB ({name})"
+        np.save(os.path.join(path, f"{name}.npy"), a)
+
+
 def cpu_baseline(c, sd_seed=7):
     """The oracle (CPU restatement, fp32, reference semantics) timed on this host's cores: ONE clip of the
     same workload, forward + backward, stochastic=False index path (multinomial is not the cost)."""
@@ -447,12 +477,21 @@ def main():
                          "reported under the extra key 'gan_step'; the headline metric is unchanged")
     ap.add_argument("--force-dist", action="store_true",
                     help="rehearsal of the N > 1 code path on one GPU: process group, DataParallelTokenizer, barriers and the MAX all-reduce at world size 1")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the host enqueue cost of a step, the roofline replays of the "
+                         "dominant GEMM, the attention kernels and the codebook search (with the committed-profile figures), the stock-PyTorch "
+                         "yardstick and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: leave out the roofline replays")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed (loss, model outputs, parameter gradients) as DIR/<name>.npy; "
+                         "same arguments, same inputs")
     ap.add_argument("--rehearse-launch", action="store_true",
                     help="launcher / rendezvous rehearsal only: every rank joins the process group (gloo when there is no GPU), "
                          "barrier + MAX all-reduce, rank 0 prints one JSON line; no model is built")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:     # bare `python bench.py --gpus N`: be our own launcher
         sys.exit(launch_ranks(a.gpus, sys.argv[1:]))
@@ -514,7 +553,7 @@ def main():
         loss.backward()
         if opt is not None:
             opt.step()
-        return loss
+        return loss, out
 
     if a.graph:
         # the whole forward + loss + backward as ONE hipGraph replay (engine.GraphedStep); the optimizer step stays outside
@@ -523,10 +562,10 @@ def main():
         graphed = GraphedStep(net, x, lambda out, xin: (out["pred_frames"] - xin).abs().mean() + 0.1 * out["loss_q"])
 
         def step():  # noqa: F811
-            loss, _ = graphed(x)
+            loss, out = graphed(x)
             if opt is not None:
                 opt.step()
-            return loss
+            return loss, out
 
     for _ in range(a.warmup):
         step()
@@ -536,7 +575,8 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        loss = step()
+        out = None      # the previous step's outputs are freed before the next step allocates its own (only the last one is kept)
+        loss, out = step()
     torch.cuda.synchronize()
     if multi:
         dist.barrier()
@@ -547,10 +587,13 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     assert torch.isfinite(loss).item(), "loss is not finite"
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, loss, out, model)
+    del out
     # host-side cost of ENQUEUEING one step, measured outside the timed region on an empty queue (a sync before each probe
     # step): inside the timed loop the host runs ahead until the HIP queue is full and then measures back-pressure instead
     host = []
-    for _ in range(3):
+    for _ in range(3 if a.full else 0):
         torch.cuda.synchronize()
         h0 = time.perf_counter()
         step()
@@ -569,10 +612,11 @@ def main():
                                    f"{c['encoder_depth']}+{c['decoder_depth']} blocks, Nq={c['bottleneck_token_num']}, d={c['bottleneck_dim']}, K={c['codebook_size']}, "
                                    f"stochastic VQ (tau 0.03), loss = L1 + 0.1*loss_q" + (f", Adam ({a.optimizer})" if opt else ""),
                        "global_batch": world * B, "parallelism": f"dp{world}"},
-            "host_enqueue_ms_per_step": round(sorted(host)[len(host) // 2] * 1e3, 3),
             "model_tflops_per_gpu": round(clips_s / world * f_clip / 1e12, 1),
             "attention_gemm_tflops_per_gpu": round(clips_s / world * f_attn / 1e12, 1),
         }
+        if host:
+            res["host_enqueue_ms_per_step"] = round(sorted(host)[len(host) // 2] * 1e3, 3)
         # the secondary legs must never cost the headline line: a failure there is reported in place of the object
         if a.gan and world == 1:
             try:
@@ -594,7 +638,7 @@ def main():
                 res["ar_prior"] = ar_prior_step(vt, a.ar, a.steps, a.warmup)
             except Exception as e:  # noqa: BLE001
                 res["ar_prior"] = {"error": repr(e)}
-        if not a.no_roofline:
+        if a.full and not a.no_roofline:
             try:
                 ach, per, _ = time_dominant_kernel(B, c)
                 res["roofline"] = {"bound": "mfma", "kernel": "gemm_nt192_kernel<VT_EPI_BF16> (qkv fwd + fc1/proj/qkv dgrad)", "achieved": round(ach, 1),
@@ -615,9 +659,9 @@ def main():
                 res["roofline"]["mfma_busy_step"] = committed_profile("mfma_busy")
             except Exception as e:  # noqa: BLE001
                 res["roofline"] = {"bound": "mfma", "achieved": None, "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": None, "traffic": None, "error": repr(e)}
-        if a.config == "B" and not a.gan and a.optimizer == "none":
+        if a.full and a.config == "B" and not a.gan and a.optimizer == "none":
             res["stock_pytorch_same_gpu"] = torch_yardstick(B)
-        if not a.no_cpu_baseline and world == 1:  # the CPU leg runs at N = 1 only (other ranks would sit in teardown meanwhile)
+        if a.full and not a.no_cpu_baseline and world == 1:  # the CPU leg runs at N = 1 only (other ranks would sit in teardown meanwhile)
             try:
                 res["cpu_baseline"] = cpu_baseline(c)
             except Exception as e:  # noqa: BLE001

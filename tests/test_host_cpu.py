@@ -445,6 +445,35 @@ def test_product_geometry_table_and_synthetic_clips_equal_the_checkers():
     assert re.search(r"^\s*from oracle import", src[start:end], re.M)
 
 
+def test_bench_dump_outputs_sample_dtypes_and_size(tmp_path):
+    """bench.py --dump-outputs: float32 arrays (float64 for integer ones), an array above DUMP_SAMPLE elements written at positions
+    that depend on its size alone (two dumps of the same outputs are identical), non-tensor entries skipped, 64 MB at most."""
+    import bench
+    m = torch.nn.Sequential(torch.nn.Linear(1024, 1100), torch.nn.Linear(1100, 8, bias=False))
+    m[1].weight.requires_grad_(False)
+    m(torch.randn(4, 1024)).sum().backward()
+    g = torch.Generator().manual_seed(0)
+    out = {"pred_frames": torch.arange(2 * 3 * 4 * 256 * 256, dtype=torch.float32).reshape(2, 3, 4, 256, 256), "bottleneck_rep": torch.randint(0, 8192, (2, 16), generator=g),
+           "h": torch.randn(3, 5, generator=g).bfloat16(), "note": "not an array"}
+    dirs = [str(tmp_path / "a"), str(tmp_path / "b")]
+    for d in dirs:
+        bench.dump_outputs(d, torch.tensor(0.25), out, m)
+    assert sorted(os.listdir(dirs[0])) == ["bottleneck_rep.npy", "grads.npy", "h.npy", "loss.npy", "pred_frames.npy"]
+    for f in os.listdir(dirs[0]):
+        assert np.array_equal(np.load(os.path.join(dirs[0], f)), np.load(os.path.join(dirs[1], f))), f
+    load = lambda n: np.load(os.path.join(dirs[0], f"{n}.npy"))  # noqa: E731
+    assert load("loss").dtype == np.float32 and load("loss") == 0.25
+    assert load("bottleneck_rep").dtype == np.float64 and np.array_equal(load("bottleneck_rep"), out["bottleneck_rep"].numpy())
+    assert load("h").dtype == np.float32 and np.array_equal(load("h"), out["h"].float().numpy())
+    pred = load("pred_frames")
+    # the values are their own flat positions: distinct positions, in order, spread over the whole array
+    assert pred.dtype == np.float32 and pred.shape == (bench.DUMP_SAMPLE,) and (np.diff(pred) > 0).all()
+    assert pred[0] < 100 and pred[-1] > out["pred_frames"].numel() - 100
+    grads = load("grads")   # the frozen weight has no gradient: 1024 * 1100 + 1100 elements, above the sample size
+    assert grads.shape == (bench.DUMP_SAMPLE,) and np.isin(grads, torch.cat([m[0].weight.grad.reshape(-1), m[0].bias.grad]).numpy()).all()
+    assert sum(os.path.getsize(os.path.join(dirs[0], f)) for f in os.listdir(dirs[0])) <= 64 << 20
+
+
 def test_sq_bottleneck_host_surface():
     """LARPTokenizer(bottleneck_type='sq') (models/larp_tokenizer.py:225-229): parameter names and shapes of the reference's
     state dict, the frozen 196 560 x 24 codebook, and the engine's parameter binding; no GPU needed to construct it."""

@@ -945,7 +945,7 @@ def test_bench_contract_and_distributed_rehearsal():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29541")
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--force-dist", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"],
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--force-dist", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"],
                          capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -959,17 +959,20 @@ def test_bench_contract_and_distributed_rehearsal():
     assert rf["bound"] == "mfma" and rf["peak"] == 2500.0 and 0.05 < rf["frac"] < 1.0 and abs(rf["frac"] - rf["achieved"] / rf["peak"]) < 1e-3
 
 
-def test_bench_own_launcher_path_on_one_gpu():
+def test_bench_own_launcher_path_on_one_gpu(tmp_path):
     """`python bench.py --gpus N` without a launcher spawns its own rank processes (bench.py::launch_ranks, the path the
     driver takes when it runs `bench.py --gpus N` bare).  Driven here with N = 1 through the same function: a
-    torch.distributed.run child, RCCL process group of one rank, one JSON line on stdout, exit code passed through."""
+    torch.distributed.run child, RCCL process group of one rank, one JSON line on stdout, exit code passed through.
+    Without --full the line carries no secondary figures; --dump-outputs writes the last timed step's outputs from rank 0."""
     import json
     import os
     import subprocess
     import sys
+    import numpy as np
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dump = str(tmp_path / "dump")
     code = ("import sys; sys.path.insert(0, %r); import bench; "
-            "sys.exit(bench.launch_ranks(1, ['--gpus', '1', '--force-dist', '--steps', '2', '--warmup', '1', '--no-cpu-baseline', '--no-roofline']))" % root)
+            "sys.exit(bench.launch_ranks(1, ['--gpus', '1', '--force-dist', '--steps', '2', '--warmup', '1', '--dump-outputs', %r]))" % (root, dump))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -977,6 +980,13 @@ def test_bench_own_launcher_path_on_one_gpu():
     assert len(lines) == 1, out.stdout[-2000:]
     r = json.loads(lines[0])
     assert r["n_gpus"] == 1 and r["value"] > 50 and r["config"]["parallelism"] == "dp1"
+    assert not {"roofline", "cpu_baseline", "stock_pytorch_same_gpu", "host_enqueue_ms_per_step"} & set(r)
+    assert abs(r["ms_per_step"] - 8e3 / r["value"]) < 0.01 * r["ms_per_step"]
+    loss, pred, idx = (np.load(os.path.join(dump, f"{n}.npy")) for n in ("loss", "pred_frames", "bottleneck_rep"))
+    assert loss.dtype == np.float32 and np.isfinite(loss) and loss > 0
+    assert pred.dtype == np.float32 and pred.shape == (1 << 20,) and np.isfinite(pred).all()
+    assert idx.dtype == np.float64 and idx.shape == (8, 1024) and idx.min() >= 0 and idx.max() < 8192
+    assert np.isfinite(np.load(os.path.join(dump, "grads.npy"))).all()
 
 
 def test_fsq_bottleneck_branch_matches_oracle():
