@@ -265,6 +265,30 @@ int vt_fsq_indices_to_codes(const int32_t* indices, int64_t N, int32_t d, const 
                             int32_t is_bf16, vtStream stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Token gate of `autoencoder_stat` (models/model_stat/autoencoder.py:69-138, base/blocks.py:11-24,89): the adaptive-length
+ * tokenizer scores each latent row with ProbPredictor = Linear(W, W) -> GELU -> Linear(W, 1) -> Sigmoid and zeroes the rows it
+ * drops before FSQ.  The first Linear + GELU is vt_gemm_nt (VT_EPI_BF16_GELU: u and g = gelu(u), bf16 [M, W] with row stride ld);
+ * these two calls are the rest.  W % 128 == 0, W <= 1024; g, u, dU, w2 16-byte aligned; probs, mask fp32 [M]; z, codes, dz,
+ * dcodes fp32 [M, d]; indices int32 [M] (may be NULL); w2 fp32 [W], b2 / db2 fp32 [1] (device).
+ *   forward:  p = bf16(sigmoid(bf16(g . w2 + b2))); mask by `mode`; codes, indices = FSQ(z * mask) exactly as vt_fsq_forward.
+ *             VT_STAT_SAMPLE keeps row m iff u_m < p with u_m a counter-hash uniform of (seed, m); VT_STAT_THRESHOLD iff p > 0.5;
+ *             VT_STAT_ONES keeps every row; VT_STAT_FORCED copies mask_in.  z == NULL: probabilities and mask only.
+ *   backward: dz = fsq'(z * mask) dcodes * mask; dp = [ste](sum_c (fsq'(z * mask) dcodes)_c z_c + dmask) + dprobs (dprobs / dmask
+ *             may be NULL); dlogit = dp p (1 - p); dU = bf16(dlogit w2 * gelu'(u)); dw2 = sum_m dlogit_m g_m, db2 = sum_m dlogit_m
+ *             (per-workgroup partials in `workspace` of vt_stat_gate_workspace_bytes(W) bytes, summed in a fixed order: no atomics,
+ *             bit-identical run to run).  `ste` = the mask is the straight-through `(mask - p).detach() + p` (sampled or forced).
+ * ------------------------------------------------------------------------------------------ */
+enum { VT_STAT_SAMPLE = 0, VT_STAT_THRESHOLD = 1, VT_STAT_ONES = 2, VT_STAT_FORCED = 3 };
+size_t vt_stat_gate_workspace_bytes(int32_t W);
+int vt_stat_gate_forward(const void* g, int64_t ldg, const float* w2, const float* b2, const float* z, int64_t M, int32_t W, int32_t d,
+                         const int32_t* levels_host, int32_t mode, uint64_t seed, const float* mask_in, float* probs, float* mask,
+                         float* codes, int32_t* indices, vtStream stream);
+int vt_stat_gate_backward(const float* dcodes, const float* dprobs, const float* dmask, const float* z, const float* mask,
+                          const float* probs, const void* u, const void* g, int64_t ld, const float* w2, int64_t M, int32_t W, int32_t d,
+                          const int32_t* levels_host, int32_t ste, void* dU, float* dz, float* dw2, float* db2, void* workspace,
+                          vtStream stream);
+
+/* ------------------------------------------------------------------------------------------
  * Glue of the TiTok-style transformer block (models/model_new/base/transformer.py:11-63, rope.py:18-24): the block's
  * GEMMs, its LayerNorm over D and the attention itself are vt_gemm_nt / vt_layernorm_* / vt_attention_*; these are the
  * HBM-bound passes in between.  All matrices bf16 row-major, 16-byte aligned; head_dim is 64 (utils.py:6), D = 64 H.

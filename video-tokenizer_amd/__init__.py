@@ -31,7 +31,7 @@ def graph_replay_safe():
 from . import hip  # noqa: F401  (ctypes binding; loading is lazy)
 from . import config  # noqa: F401
 from .registry import make, models, register  # noqa: F401
-from . import transformer, bottleneck, larp_tokenizer, loss, titok, sq, larp_ar  # noqa: F401  (registers the classes)
+from . import transformer, bottleneck, larp_tokenizer, loss, titok, stat, sq, larp_ar  # noqa: F401  (registers the classes)
 from .larp_tokenizer import LARPTokenizer  # noqa: F401
 from .larp_ar import LARP_AR  # noqa: F401
 from .loss import TransformerDiscriminator, VQLPIPSWithDiscriminator  # noqa: F401

@@ -161,6 +161,14 @@ __device__ __forceinline__ float gelu_erf_grad(float x) {
     return fmaf(x * 0.39894228040143267794f, e, cdf);
 }
 
+// PCG-style integer hash (one round of pcg32's output permutation): the counter-based random numbers of the stochastic
+// codebook search (vt_vq.hip) and of the token gate's Bernoulli draw (vt_stat.hip)
+__device__ __forceinline__ unsigned pcg_hash(unsigned v) {
+    const unsigned state = v * 747796405u + 2891336453u;
+    const unsigned word = ((state >> ((state >> 28u) + 4u)) ^ state) * 277803737u;
+    return (word >> 22u) ^ word;
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);

@@ -11,45 +11,15 @@
 // All arithmetic is fp32 in the reference's operation order (the forward runs with autocast disabled, :119-131), so
 // indices are bit-exact against oracle/fsq_oracle.c.  tanh is evaluated in double and rounded -- N*d is a few tens
 // of thousands of elements, the fp64 rate is irrelevant next to the launch itself -- which gives the correctly
-// rounded fp32 tanh, the same value the oracle computes with libm.
+// rounded fp32 tanh, the same value the oracle computes with libm.  The per-element arithmetic lives in vt_fsq_device.h.
 #include "vt_common.h"
-
-#include <cmath>
-
-#define FSQ_MAX_D 16
+#include "vt_fsq_device.h"   // FsqConsts, fsq_make_consts and the per-element arithmetic (shared with vt_stat.hip)
 
 namespace {
 #pragma clang fp contract(off)
 
-struct FsqConsts {
-    int d;
-    int levels[FSQ_MAX_D];
-    int basis[FSQ_MAX_D];
-    float half_l[FSQ_MAX_D], offset[FSQ_MAX_D], shift[FSQ_MAX_D], half_width[FSQ_MAX_D];
-};
-
-// host side of fsq.py:62-73,78-80; identical to oracle/fsq_oracle.c:fsq_constants
-bool make_consts(const int32_t* levels, int d, FsqConsts& k) {
-    int64_t b = 1;
-    k.d = d;
-    for (int c = 0; c < d; ++c) {
-        if (levels[c] < 2) return false;
-        k.levels[c] = levels[c];
-        k.half_l[c] = (float)(levels[c] - 1) * (float)(1.0 + 1e-3) / 2.0f;
-        k.offset[c] = (levels[c] % 2 == 0) ? 0.5f : 0.0f;
-        k.shift[c] = (float)atanh((double)(k.offset[c] / k.half_l[c]));
-        k.half_width[c] = (float)(levels[c] / 2);
-        k.basis[c] = (int)b;
-        b *= levels[c];
-        if (b > (1 << 24)) return false;  // the reference sums level indices in fp32: exact only below 2^24
-    }
-    return true;
-}
-
 template <typename T> __device__ __forceinline__ float ld(const T* p, int64_t i) { return (float)p[i]; }
 template <typename T> __device__ __forceinline__ void st(T* p, int64_t i, float v) { p[i] = (T)v; }
-
-__device__ __forceinline__ float tanh_rn(float x) { return (float)tanh((double)x); }
 
 template <typename T>
 __global__ __launch_bounds__(256) void fsq_fwd_kernel(const T* __restrict__ z, int64_t N, FsqConsts k, T* __restrict__ codes,
@@ -58,11 +28,9 @@ __global__ __launch_bounds__(256) void fsq_fwd_kernel(const T* __restrict__ z, i
     if (n >= N) return;
     float acc = 0.0f;
     for (int c = 0; c < k.d; ++c) {
-        const float t = tanh_rn(ld(z, n * k.d + c) + k.shift[c]);
-        const float bounded = t * k.half_l[c] - k.offset[c];
-        const float code = __fdiv_rn(rintf(bounded), k.half_width[c]);
+        const float code = fsq_code(ld(z, n * k.d + c), k, c);
         st(codes, n * k.d + c, code);
-        acc = acc + (code * k.half_width[c] + k.half_width[c]) * (float)k.basis[c];
+        acc = acc + fsq_index_term(code, k, c);
     }
     if (indices) indices[n] = (int32_t)acc;
 }
@@ -73,9 +41,7 @@ __global__ __launch_bounds__(256) void fsq_bwd_kernel(const T* __restrict__ z, c
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= total) return;
     const int c = (int)(i % k.d);
-    const float t = tanh_rn(ld(z, i) + k.shift[c]);
-    const float g = __fdiv_rn(ld(dcodes, i), k.half_width[c]);
-    st(dz, i, (g * k.half_l[c]) * (1.0f - t * t));
+    st(dz, i, fsq_grad(ld(z, i), ld(dcodes, i), k, c));
 }
 
 template <typename T>
@@ -89,14 +55,14 @@ __global__ __launch_bounds__(256) void fsq_i2c_kernel(const int32_t* __restrict_
 
 int check(const char* name, int64_t N, int d, const int32_t* levels_host, FsqConsts& k) {
     VT_CHECK_ARG(N > 0 && d >= 1 && d <= FSQ_MAX_D && levels_host, "%s: need N > 0, 1 <= d <= %d and a host levels array", name, FSQ_MAX_D);
-    VT_CHECK_ARG(make_consts(levels_host, d, k), "%s: every level must be >= 2 and prod(levels) <= 2^24", name);
+    VT_CHECK_ARG(fsq_make_consts(levels_host, d, k), "%s: every level must be >= 2 and prod(levels) <= 2^24", name);
     return VT_OK;
 }
 }  // namespace
 
 extern "C" int vt_fsq_codebook_size(const int32_t* levels_host, int32_t d, int64_t* size) {
     FsqConsts k;
-    VT_CHECK_ARG(levels_host && size && d >= 1 && d <= FSQ_MAX_D && make_consts(levels_host, d, k), "vt_fsq_codebook_size: bad levels");
+    VT_CHECK_ARG(levels_host && size && d >= 1 && d <= FSQ_MAX_D && fsq_make_consts(levels_host, d, k), "vt_fsq_codebook_size: bad levels");
     *size = (int64_t)k.basis[d - 1] * levels_host[d - 1];
     return VT_OK;
 }

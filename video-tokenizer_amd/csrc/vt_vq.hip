@@ -73,12 +73,6 @@ __global__ void vq_prep_tokens_kernel(const float* __restrict__ zin, int64_t ldz
     znorm[n] = den;
 }
 
-__device__ __forceinline__ unsigned pcg_hash(unsigned v) {
-    const unsigned state = v * 747796405u + 2891336453u;
-    const unsigned word = ((state >> ((state >> 28u) + 4u)) ^ state) * 277803737u;
-    return (word >> 22u) ^ word;
-}
-
 // Gumbel(0,1) noise from a counter-based hash of (seed, token, code): argmax(logit + G) is a draw from
 // softmax(logit) == torch.multinomial(softmax(.), 1)  (bottleneck.py:276-280), in one pass.
 // The per-call counter (seed_lo) is hashed on its own before the token index is added: with token ^ seed_lo the noise vector of

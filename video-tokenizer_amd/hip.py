@@ -82,6 +82,11 @@ SIGNATURES = {
     "vt_fsq_forward": (c_i32, [c_vp, c_i32, c_i64, c_i32, ctypes.POINTER(c_i32), c_vp, c_vp, c_vp]),
     "vt_fsq_backward": (c_i32, [c_vp, c_vp, c_i32, c_i64, c_i32, ctypes.POINTER(c_i32), c_vp, c_vp]),
     "vt_fsq_indices_to_codes": (c_i32, [c_vp, c_i64, c_i32, ctypes.POINTER(c_i32), c_vp, c_i32, c_vp]),
+    "vt_stat_gate_workspace_bytes": (c_sz, [c_i32]),
+    "vt_stat_gate_forward": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, ctypes.POINTER(c_i32), c_i32, c_u64, c_vp, c_vp, c_vp,
+                                     c_vp, c_vp, c_vp]),
+    "vt_stat_gate_backward": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i32, c_i32, ctypes.POINTER(c_i32), c_i32,
+                                      c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "vt_qknorm_rope_fwd": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp]),
     "vt_qknorm_rope_bwd_workspace_bytes": (c_sz, []),
     "vt_qknorm_rope_bwd": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
@@ -577,6 +582,47 @@ def fsq_indices_to_codes(indices, levels, dtype=torch.float32):
     codes = torch.empty(*idx.shape, d, device=idx.device, dtype=dtype)
     check(lib().vt_fsq_indices_to_codes(ptr(idx), idx.numel(), d, _levels(levels), ptr(codes), _fsq_dtype(codes), stream()), "vt_fsq_indices_to_codes")
     return codes
+
+
+# ---- token gate of autoencoder_stat (csrc/vt_stat.hip) ----
+STAT_SAMPLE, STAT_THRESHOLD, STAT_ONES, STAT_FORCED = 0, 1, 2, 3
+
+
+def stat_gate_forward(g, w2, b2, z, levels, mode, seed=0, mask_in=None):
+    """g bf16 [M, W] (gelu of the head's fc1), w2 fp32 [W], b2 fp32 [1], z fp32 [M, d] or None -> (probs, mask fp32 [M],
+    codes fp32 [M, d], indices int32 [M]); codes / indices are None when z is None"""
+    require_gpu(g, w2, b2, z, mask_in)
+    M, W = g.shape
+    assert g.dtype == torch.bfloat16 and g.stride(1) == 1 and w2.is_contiguous() and w2.dtype == torch.float32
+    dev = g.device
+    probs, mask = torch.empty(M, device=dev), torch.empty(M, device=dev)
+    codes = idx = None
+    d = len(levels) if levels is not None else 0
+    if z is not None:
+        assert z.is_contiguous() and z.dtype == torch.float32 and tuple(z.shape) == (M, d)
+        codes = torch.empty_like(z)
+        idx = torch.empty(M, device=dev, dtype=torch.int32)
+    check(lib().vt_stat_gate_forward(ptr(g), g.stride(0), ptr(w2), ptr(b2), ptr(z), M, W, d, _levels(levels or []), int(mode),
+                                     int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(mask_in), ptr(probs), ptr(mask), ptr(codes), ptr(idx), stream()),
+          "vt_stat_gate_forward")
+    return probs, mask, codes, idx
+
+
+def stat_gate_backward(dcodes, dprobs, dmask, z, mask, probs, u, g, w2, levels, ste):
+    """-> (dU bf16 [M, W], dz fp32 [M, d] or None, dw2 fp32 [W], db2 fp32 [1]); dprobs / dmask may be None"""
+    require_gpu(dcodes, dprobs, dmask, z, mask, probs, u, g, w2)
+    M, W = g.shape
+    assert u.shape == g.shape and u.is_contiguous() and g.is_contiguous() and u.dtype == g.dtype == torch.bfloat16
+    dev = g.device
+    dU = torch.empty(M, W, device=dev, dtype=torch.bfloat16)
+    dz = torch.empty_like(z) if z is not None else None
+    dw2, db2 = torch.empty(W, device=dev), torch.empty(1, device=dev)
+    d = len(levels) if levels is not None else 0
+    ws = _ws(lib().vt_stat_gate_workspace_bytes(W), dev)
+    check(lib().vt_stat_gate_backward(ptr(dcodes), ptr(dprobs), ptr(dmask), ptr(z), ptr(mask), ptr(probs), ptr(u), ptr(g), W, ptr(w2), M, W, d,
+                                      _levels(levels or []), int(bool(ste)), ptr(dU), ptr(dz), ptr(dw2), ptr(db2), ptr(ws), stream()),
+          "vt_stat_gate_backward")
+    return dU, dz, dw2, db2
 
 
 # ---- glue of the TiTok-style block (csrc/vt_gated.hip) ----
