@@ -289,6 +289,31 @@ int vt_stat_gate_backward(const float* dcodes, const float* dprobs, const float*
                           vtStream stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Diagonal-Gaussian KL bottleneck: the 'skl' regularizer (`SummedKLDivergenceRegularizer` over
+ * `DiagonalGaussianDistribution`, models/bottleneck.py:36-64, 347-375) between in_linear and out_linear.
+ * z fp32 [M, ldz] holds 2d interleaved columns: mean = z[:, 0::2], logvar = clamp(z[:, 1::2], -30, 20) (bounds inclusive).
+ *   forward:  eps = standard normal from a counter hash of (seed, *seed_counter, element index r * d + c) (Box-Muller on element
+ *             pairs; seed_counter is device memory and may be NULL, the low seed word plus *seed_counter as in vt_vq_forward_ctr, so
+ *             a replayed hipGraph draws fresh noise and eager / replayed calls draw the same sequence); sample = mean + exp(logvar/2) eps
+ *             (the reference always samples, in eval mode too).  Writes mean, sample, noise fp32 [M, d] (each may be NULL), the bf16
+ *             copy of sample with row stride ldp, columns d..ldp zeroed (may be NULL), and loss_kl[0] = sum_{r,c} 0.5 (mean^2 +
+ *             exp(logvar) - 1 - logvar) / batch (the per-sample sum averaged over `batch` = M / rows per sample).  The sum runs over
+ *             per-workgroup partials in `workspace` (VT_KL_WORKSPACE_BYTES) in a fixed order: no float atomics, bit-identical run to run.
+ *   backward: g_sample = dL/dsample [M, ldg] (may be NULL), g_mean = dL/dmean [M, d] (may be NULL), gkl = device {dL/dloss_kl}
+ *             (may be NULL); dmean = g_sample + g_mean + (gkl / batch) mean, dlogvar_raw = [-30 <= z_odd <= 20] (g_sample eps std / 2
+ *             + (gkl / batch) (var - 1) / 2) -> dz fp32 [M, 2d] interleaved and / or its bf16 copy with row stride ldp >= 2d, columns
+ *             2d..ldp zeroed (either may be NULL, not both).
+ * d % 4 == 0 (8, 16, 24, 32 on the engine), M % batch == 0; z, mean, sample, noise, dz 16-byte aligned, ldz % 4 == 0; bf16 outputs,
+ * g_sample and g_mean 8-byte aligned, ldp % 4 == 0, ldg % 2 == 0.  Checked on the host: VT_ERR_INVALID + vt_last_error.
+ * ------------------------------------------------------------------------------------------ */
+#define VT_KL_WORKSPACE_BYTES 4096
+int vt_kl_forward(const float* z, int64_t ldz, int64_t M, int32_t d, int32_t batch, uint64_t seed, const uint32_t* seed_counter,
+                  float* mean, float* sample, void* sample_pad_bf16, int64_t ldp, float* noise, float* loss_kl, void* workspace,
+                  vtStream stream);
+int vt_kl_backward(const float* g_sample, int64_t ldg, const float* g_mean, const float* gkl, const float* z, int64_t ldz,
+                   const float* noise, int64_t M, int32_t d, int32_t batch, float* dz, void* dz_pad_bf16, int64_t ldp, vtStream stream);
+
+/* ------------------------------------------------------------------------------------------
  * Glue of the TiTok-style transformer block (models/model_new/base/transformer.py:11-63, rope.py:18-24): the block's
  * GEMMs, its LayerNorm over D and the attention itself are vt_gemm_nt / vt_layernorm_* / vt_attention_*; these are the
  * HBM-bound passes in between.  All matrices bf16 row-major, 16-byte aligned; head_dim is 64 (utils.py:6), D = 64 H.
@@ -495,6 +520,24 @@ int vt_tokenizer_set_data_parallel(vtTokenizer* tk, int32_t on);
 int vt_tokenizer_backward_until_flush(vtTokenizer* tk, const vtTokenizerTensors* params, const float* d_pred, const float* gscal,
                                       void* workspace, const vtTokenizerTensors* grads, int32_t stage_begin, int32_t* stage_next,
                                       int32_t* final_through, vtStream stream);
+
+/* The same engine with the KL bottleneck ('skl', see vt_kl_forward) instead of VQ: in_linear has 2d outputs (in_w [2d, D], in_b [2d]),
+ * vt_kl_forward / vt_kl_backward take the place of the quantizer.  vt_tokenizer_create_kl ignores K, vq_mode, l2_normalized, inv_tau,
+ * beta, codebook_w and freeze_codebook.  A KL handle works with pack, decode, backward, backward_until_flush, set_seed_counter and
+ * every set_* option; there params.codebook is NULL and gscal = device {dL/dloss_kl} or NULL.  vt_tokenizer_encode and
+ * vt_tokenizer_codes_to_encoded on a KL handle, and vt_tokenizer_encode_kl on a VQ handle, return VT_ERR_INVALID. */
+typedef struct {                          /* forward outputs of a KL handle (device, caller-owned)    */
+    float* encoded;                       /* [B,Nq,D]  'encoded' = out_linear(sample)                  */
+    float* mean;                          /* [B*Nq,d]  'bottleneck_rep' (may be NULL)                  */
+    float* projected_z;                   /* [B*Nq,2d] in_linear output (may be NULL)                  */
+    float* regularized_z;                 /* [B*Nq,d]  the sample (may be NULL)                        */
+    float* noise;                         /* [B*Nq,d]  eps of the sample (may be NULL)                 */
+    float* loss_kl;                       /* [1]                                                       */
+    float* input_norms;                   /* [2] input_norm_first, input_norm_last (may be NULL)       */
+} vtTokenizerKLOutputs;
+int vt_tokenizer_create_kl(const vtTokenizerConfig* cfg, vtTokenizer** out);
+int vt_tokenizer_encode_kl(vtTokenizer* tk, const vtTokenizerTensors* params, const float* video, void* workspace,
+                           const vtTokenizerKLOutputs* out, uint64_t seed, vtStream stream);
 
 /* ------------------------------------------------------------------------------------------
  * A stack of timm Blocks on its own (fp32 [B, L, D] in and out): `transformer_encoder_parallel` / `_fused` called

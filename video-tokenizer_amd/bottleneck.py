@@ -1,16 +1,72 @@
-"""Bottleneck + vector quantiser: parameter holders and option surface.
+"""Bottleneck + vector quantiser / KL regulariser: parameter holders and option surface.
 
 Mirrors /root/reference/models/bottleneck.py: `Bottleneck` (:65-188; in_linear -> regulariser ->
 out_linear; norm 'none' on the fused engine, the LayerNorm / SyncBatchNorm variants as torch glue on the composed path) and `SimpleVectorQuantizer` (:203-344; l2-normalised cosine / L2
-codebook search in three index modes).  State-dict keys: `in_linear.*`, `out_linear.*`,
-`regularizer.embedding.weight`.  Arithmetic: vt_vq_forward / vt_vq_backward + GEMMs -- fused inside the
+codebook search in three index modes), `SummedKLDivergenceRegularizer` ('skl', :347-375: a diagonal Gaussian over the
+2d-wide in_linear output, sampled by reparameterisation, summed KL loss) with `DiagonalGaussianDistribution` (:36-64).
+State-dict keys: `in_linear.*`, `out_linear.*`, `regularizer.embedding.weight` ('vq' only).  Arithmetic: vt_vq_forward / vt_vq_backward + GEMMs -- fused inside the
 engine when called through LARPTokenizer, through functional.{Linear,VectorQuantize} when the modules are
 called on their own (forward / decode / get_codebook_entry keep the reference's signatures and dict keys).
 """
+import numpy as np
 import torch
 import torch.nn as nn
 
 from .registry import make, register
+
+
+class DiagonalGaussianDistribution:
+    """bottleneck.py:36-64: mean = parameters[..., 0::2], logvar = clamp(parameters[..., 1::2], -30, 20).  Torch glue over a [B, N, 2d]
+    tensor (the 'skl' output `dist`); the regularizer's own sample and loss come from the fused kernels (vt_kl_forward), not from here."""
+
+    def __init__(self, parameters, deterministic=True):
+        self.device = parameters.device
+        self.deterministic = deterministic
+        self.mean, self.logvar = parameters[..., ::2], parameters[..., 1::2]
+        self.logvar = torch.clamp(self.logvar, -30.0, 20.0)
+        self.std = torch.exp(0.5 * self.logvar)
+        self.var = torch.exp(self.logvar)
+
+    def sample(self):
+        if self.deterministic:
+            return self.mean
+        return self.mean + self.std * torch.randn(self.mean.shape).to(device=self.device)
+
+    def kl(self):
+        return 0.5 * (torch.pow(self.mean, 2) + self.var - 1.0 - self.logvar)
+
+    def nll(self, sample, dims=[1]):
+        logtwopi = np.log(2.0 * np.pi)
+        return 0.5 * torch.sum(logtwopi + self.logvar + torch.pow(sample - self.mean, 2) / self.var, dim=dims)
+
+    def mode(self):
+        return self.mean
+
+
+@register("skl")
+class SummedKLDivergenceRegularizer(nn.Module):
+    """bottleneck.py:347-375, the latent-diffusion KL bottleneck: z [B, N, 2d] -> sample = mean + std * eps (always sampled, eval mode
+    too), loss_kl = sum over (N, d) of the KL to N(0, 1), averaged over the batch; bottleneck_rep = mean; decode = identity.  One
+    vt_kl_forward / vt_kl_backward pair (functional.KLSample); eps is a counter-hash Gaussian seeded from torch.initial_seed() and a
+    per-module call counter, kept as `last_noise` for inspection."""
+
+    def __init__(self, dim, **kwargs):
+        super().__init__()
+        self.dim = dim
+        self.last_noise = None
+
+    def forward(self, z):
+        from .functional import KLSample
+        assert len(z.shape) == 3, "Input shape must be (batch, n_tokens, dim)"
+        assert z.shape[-1] == self.dim * 2, "Input shape must be (batch, n_tokens, 2 * dim)"
+        self._calls = getattr(self, "_calls", 0) + 1
+        seed = (torch.initial_seed() * 0x9E3779B97F4A7C15 + self._calls) & 0xFFFFFFFFFFFFFFFF
+        sample, mean, loss_kl, noise = KLSample.apply(z, seed)
+        self.last_noise = noise
+        return {"regularized_z": sample, "bottleneck_rep": mean, "dist": DiagonalGaussianDistribution(z, deterministic=False), "loss_kl": loss_kl}
+
+    def decode(self, z_bottleneck):
+        return z_bottleneck
 
 
 @register("vq")
@@ -121,9 +177,11 @@ class Bottleneck(nn.Module):
         if norm not in (None, "ln_d", "ln_nd", "ln_d_na", "bn_bn", "bn_b"):
             raise ValueError(f"Normalization type {norm} not supported")
         self.norm = norm
-        if regularizer is None or regularizer["name"].lower() != "vq":
-            raise NotImplementedError("only the 'vq' regularizer is built")
-        self.project_dim = self.bottleneck_dim
+        name = regularizer["name"].lower() if regularizer is not None else None
+        if name not in ("vq", "skl"):
+            raise NotImplementedError(f"regularizer {name!r}: the 'vq' and 'skl' regularizers are built")
+        # bottleneck.py:98-101: a '*kl*' regularizer (except 'vqkl') reads mean and log-variance from 2d projected columns
+        self.project_dim = self.bottleneck_dim * 2 if name == "skl" else self.bottleneck_dim
         self.in_linear = nn.Linear(self.input_dim, self.project_dim)
         self.out_linear = nn.Linear(self.bottleneck_dim, self.output_dim)
         # bottleneck.py:113-126: LayerNorm over the d (or token x d) entries of the projected latents, fp32 with autocast off (:146-159).

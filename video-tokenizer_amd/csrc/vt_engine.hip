@@ -17,6 +17,15 @@
 
 #include "vt_common.h"
 
+// The KL bottleneck's kernels (vt_kl.hip) are referenced weakly: the library resolves them, a link of the engine without vt_kl.o
+// (a host-side test harness that only models the VQ path) still loads, and vt_tokenizer_create_kl refuses to build a KL handle there.
+extern "C" int vt_kl_forward(const float* z, int64_t ldz, int64_t M, int32_t d, int32_t batch, uint64_t seed, const uint32_t* seed_counter,
+                             float* mean, float* sample, void* sample_pad_bf16, int64_t ldp, float* noise, float* loss_kl, void* workspace,
+                             vtStream stream) __attribute__((weak));
+extern "C" int vt_kl_backward(const float* g_sample, int64_t ldg, const float* g_mean, const float* gkl, const float* z, int64_t ldz,
+                              const float* noise, int64_t M, int32_t d, int32_t batch, float* dz, void* dz_pad_bf16, int64_t ldp,
+                              vtStream stream) __attribute__((weak));
+
 static const bool g_no_splitk = [] { const char* e = getenv("VT_GEMM_SPLITK"); return e && strcmp(e, "0") == 0; }();   // A/B switch, read once
 
 namespace {
@@ -94,6 +103,8 @@ struct vtTokenizer {
     std::vector<size_t> x_enc, x_dec;  // residual stream at block boundaries (depth+1 each)
     size_t patches, zb, zproj, vq_E, vq_wnorm, vq_zn, vq_znorm, vq_idx, vq_rz, vq_rzpad, vq_losses, vq_ws, encoded_int;
     size_t hN, meanH, rstdH, yrows;
+    bool kl = false;                         // vt_tokenizer_create_kl: KL bottleneck ('skl') in place of the quantizer; in_linear has 2d outputs
+    size_t kl_noise = 0, kl_ws = 0;          // eps of the last forward (read by the backward), loss partial sums of vt_kl_forward
     // backward scratch
     size_t dX, dh, dob, delta, ln_ws, cs_ws, cs_part, dY, dhN, dEncb, d_rz, dz_pad, dTok, tmp_vec, wg_slabs;
     const uint32_t* seed_ctr = nullptr;   // device-side per-call counter of the stochastic VQ (graph replay), see vt_vq_forward_ctr
@@ -164,17 +175,20 @@ static void plan_blocks(vtTokenizer* t, Arena& a, std::vector<BlockBufs>& v, int
     }
 }
 
-extern "C" int vt_tokenizer_create(const vtTokenizerConfig* cfg, vtTokenizer** out) {
-    VT_CHECK_ARG(cfg && out, "vt_tokenizer_create: null pointer");
+static int create_tokenizer(const vtTokenizerConfig* cfg, bool kl, vtTokenizer** out) {
+    const char* fn = kl ? "vt_tokenizer_create_kl" : "vt_tokenizer_create";
+    VT_CHECK_ARG(cfg && out, "%s: null pointer", fn);
     const vtTokenizerConfig& c = *cfg;
-    VT_CHECK_ARG(c.B > 0 && c.C > 0 && c.T > 0 && c.S > 0 && c.pt > 0 && c.p > 0, "vt_tokenizer_create: bad geometry");
-    VT_CHECK_ARG(c.T % c.pt == 0 && c.S % c.p == 0 && c.p % 8 == 0, "vt_tokenizer_create: T%%pt, S%%p, p%%8 must be 0");
-    VT_CHECK_ARG(c.D % 256 == 0 && c.D <= 1024 && c.H * 64 == c.D, "vt_tokenizer_create: D=%d H=%d unsupported (head_dim must be 64, D in 256..1024)", c.D, c.H);
-    VT_CHECK_ARG(c.depth_enc > 0 && c.depth_dec > 0 && c.Nq > 0 && c.K > 0, "vt_tokenizer_create: bad depth/Nq/K");
-    VT_CHECK_ARG(c.d == 8 || c.d == 16 || c.d == 24 || c.d == 32, "vt_tokenizer_create: bottleneck_dim %d unsupported (8,16,24,32)", c.d);
-    VT_CHECK_ARG((c.C * c.pt * c.p * c.p) % 64 == 0, "vt_tokenizer_create: patch volume must be a multiple of 64");
+    VT_CHECK_ARG(c.B > 0 && c.C > 0 && c.T > 0 && c.S > 0 && c.pt > 0 && c.p > 0, "%s: bad geometry", fn);
+    VT_CHECK_ARG(c.T % c.pt == 0 && c.S % c.p == 0 && c.p % 8 == 0, "%s: T%%pt, S%%p, p%%8 must be 0", fn);
+    VT_CHECK_ARG(c.D % 256 == 0 && c.D <= 1024 && c.H * 64 == c.D, "%s: D=%d H=%d unsupported (head_dim must be 64, D in 256..1024)", fn, c.D, c.H);
+    VT_CHECK_ARG(c.depth_enc > 0 && c.depth_dec > 0 && c.Nq > 0 && (kl || c.K > 0), "%s: bad depth/Nq/K", fn);
+    VT_CHECK_ARG(c.d == 8 || c.d == 16 || c.d == 24 || c.d == 32, "%s: bottleneck_dim %d unsupported (8,16,24,32)", fn, c.d);
+    VT_CHECK_ARG((c.C * c.pt * c.p * c.p) % 64 == 0, "%s: patch volume must be a multiple of 64", fn);
+    VT_CHECK_ARG(!kl || (vt_kl_forward && vt_kl_backward), "%s: the KL kernels (vt_kl.hip) are not linked into this library", fn);
     vtTokenizer* t = new vtTokenizer();
     t->c = c;
+    t->kl = kl;
     t->Nv = (c.T / c.pt) * (c.S / c.p) * (c.S / c.p);
     t->L = t->Nv + c.Nq;
     t->M = c.B * t->L; t->Mp = round_up(t->M, 128);
@@ -208,10 +222,17 @@ extern "C" int vt_tokenizer_create(const vtTokenizerConfig* cfg, vtTokenizer** o
     t->patches = a.take(Mvp * Kp * 2);
     t->zb = a.take(Mqp * D * 2);
     t->zproj = a.take(Mqp * 64 * 4);
-    t->vq_E = a.take((size_t)c.K * c.d * 4); t->vq_wnorm = a.take((size_t)c.K * 4);
-    t->vq_zn = a.take(Mqp * c.d * 4); t->vq_znorm = a.take(Mqp * 4); t->vq_idx = a.take(Mqp * 8);
-    t->vq_rz = a.take(Mqp * c.d * 4); t->vq_rzpad = a.take(Mqp * 64 * 2); t->vq_losses = a.take(64);
-    t->vq_ws = a.take(vt_vq_workspace_bytes(t->Mq, c.K, c.d));
+    if (kl) {
+        // the bf16 sample (out_linear operand) lives in vq_rzpad; the quantizer's buffers are not planned
+        t->vq_E = t->vq_wnorm = t->vq_zn = t->vq_znorm = t->vq_idx = t->vq_rz = t->vq_losses = t->vq_ws = 0;
+        t->vq_rzpad = a.take(Mqp * 64 * 2);
+        t->kl_noise = a.take(Mqp * c.d * 4); t->kl_ws = a.take(VT_KL_WORKSPACE_BYTES);
+    } else {
+        t->vq_E = a.take((size_t)c.K * c.d * 4); t->vq_wnorm = a.take((size_t)c.K * 4);
+        t->vq_zn = a.take(Mqp * c.d * 4); t->vq_znorm = a.take(Mqp * 4); t->vq_idx = a.take(Mqp * 8);
+        t->vq_rz = a.take(Mqp * c.d * 4); t->vq_rzpad = a.take(Mqp * 64 * 2); t->vq_losses = a.take(64);
+        t->vq_ws = a.take(vt_vq_workspace_bytes(t->Mq, c.K, c.d));
+    }
     t->encoded_int = a.take(Mqp * D * 4);
     t->hN = a.take(Mvp * D * 2); t->meanH = a.take(Mvp * 4); t->rstdH = a.take(Mvp * 4);
     t->yrows = a.take(Mvp * Kp * 4);
@@ -247,6 +268,9 @@ extern "C" int vt_tokenizer_create(const vtTokenizerConfig* cfg, vtTokenizer** o
     *out = t;
     return VT_OK;
 }
+
+extern "C" int vt_tokenizer_create(const vtTokenizerConfig* cfg, vtTokenizer** out) { return create_tokenizer(cfg, false, out); }
+extern "C" int vt_tokenizer_create_kl(const vtTokenizerConfig* cfg, vtTokenizer** out) { return create_tokenizer(cfg, true, out); }
 
 extern "C" void vt_tokenizer_destroy(vtTokenizer* t) { delete t; }
 extern "C" size_t vt_tokenizer_workspace_bytes(const vtTokenizer* t) { return t ? t->ws_bytes : 0; }
@@ -364,7 +388,7 @@ extern "C" int vt_tokenizer_pack(vtTokenizer* t, const vtTokenizerTensors* P, vo
     const int D = c.D, Kp = t->Kp;
     std::vector<vtPackJob> jobs;   // every bf16 operand copy of the model: 4 grouped launches instead of ~100 single ones
     jobs.push_back(pack_job(P->pe_w, D, Kp, nullptr, WS(void, t->pe_wb), Kp, nullptr, 0));
-    jobs.push_back(pack_job(P->in_w, c.d, D, nullptr, WS(void, t->in_wb), D, WS(void, t->in_wt), 64));    // [d,D] and [D,64]
+    jobs.push_back(pack_job(P->in_w, t->kl ? 2 * c.d : c.d, D, nullptr, WS(void, t->in_wb), D, WS(void, t->in_wt), 64));    // [d,D] and [D,64] (KL: 2d rows)
     jobs.push_back(pack_job(P->out_w, D, c.d, nullptr, WS(void, t->out_wb), 64, WS(void, t->out_wt), D));  // [D,64] and [64,D]
     jobs.push_back(pack_job(P->head_w, Kp, D, WS(int32_t, t->perm), WS(void, t->head_wb), D, WS(void, t->head_wt), Kp));
     pack_block_jobs(t, t->enc, P->enc_blocks, ws, jobs);
@@ -442,11 +466,9 @@ static int block_forward_last(vtTokenizer* t, const vtTokenizer::LastBlock& lb, 
     return VT_OK;
 }
 
-extern "C" int vt_tokenizer_encode(vtTokenizer* t, const vtTokenizerTensors* P, const float* video, void* ws,
-                                   const vtTokenizerOutputs* out, uint64_t seed, vtStream s) {
-    VT_CHECK_ARG(t && P && video && ws && out, "vt_tokenizer_encode: null pointer");
-    t->in_backward = false;
-    VT_CHECK_ARG(out->encoded && out->indices && out->losses, "vt_tokenizer_encode: encoded/indices/losses outputs are required");
+// encode up to the bottleneck's in_linear: patch embed, encoder blocks, the two norm statistics, z = in_linear(latent rows) into zproj
+// (fp32, row stride 64; d columns, 2d for a KL handle)
+static int encode_trunk(vtTokenizer* t, const vtTokenizerTensors* P, const float* video, void* ws, float* input_norms, vtStream s) {
     const vtTokenizerConfig& c = t->c;
     const int D = c.D, L = t->L, Nv = t->Nv, Nq = c.Nq;
     // 1. patchify + patch-embed GEMM (+bias +sincos PE) written straight into rows [0,Nv) of every sequence
@@ -467,13 +489,25 @@ extern "C" int vt_tokenizer_encode(vtTokenizer* t, const vtTokenizerTensors* P, 
     }
     const float* xe = WS(float, t->x_enc[c.depth_enc]);
     const vtRowMap qmap = {Nq, L, Nv};  // the last Nq rows of every sequence (transformer.py:69)
-    // 4. bottleneck: norm stats, in_linear, VQ, out_linear
-    if (out->input_norms)
-        hipLaunchKernelGGL(rownorm_mean_kernel, dim3(2), dim3(512), 0, (hipStream_t)s, xe, (int64_t)L, (int64_t)Nv, (int64_t)L - 1, c.B, D, out->input_norms);
+    // 4. bottleneck: norm stats, in_linear (the regularizer and out_linear follow in the caller)
+    if (input_norms)
+        hipLaunchKernelGGL(rownorm_mean_kernel, dim3(2), dim3(512), 0, (hipStream_t)s, xe, (int64_t)L, (int64_t)Nv, (int64_t)L - 1, c.B, D, input_norms);
     TRY(vt_cast_rows(xe, qmap, t->Mq, D, WS(void, t->zb), D, s));
-    g = nt(t, ws, WS(void, t->zb), D, WS(void, t->in_wb), D, t->Mq, c.d, D, VT_EPI_F32, WS(void, t->zproj), 64);
+    g = nt(t, ws, WS(void, t->zb), D, WS(void, t->in_wb), D, t->Mq, t->kl ? 2 * c.d : c.d, D, VT_EPI_F32, WS(void, t->zproj), 64);
     g.bias = P->in_b; g.round_bf16 = 1;
-    TRY(vt_gemm_nt(&g, s));
+    return vt_gemm_nt(&g, s);
+}
+
+extern "C" int vt_tokenizer_encode(vtTokenizer* t, const vtTokenizerTensors* P, const float* video, void* ws,
+                                   const vtTokenizerOutputs* out, uint64_t seed, vtStream s) {
+    VT_CHECK_ARG(t && P && video && ws && out, "vt_tokenizer_encode: null pointer");
+    VT_CHECK_ARG(!t->kl, "vt_tokenizer_encode: the handle has the KL bottleneck (vt_tokenizer_create_kl): use vt_tokenizer_encode_kl");
+    t->in_backward = false;
+    VT_CHECK_ARG(out->encoded && out->indices && out->losses, "vt_tokenizer_encode: encoded/indices/losses outputs are required");
+    const vtTokenizerConfig& c = t->c;
+    const int D = c.D;
+    TRY(encode_trunk(t, P, video, ws, out->input_norms, s));
+    vtGemmNT g;
     if (out->projected_z)
         hipLaunchKernelGGL(compact_cols_kernel, dim3((t->Mq * c.d + 255) / 256), dim3(256), 0, (hipStream_t)s, WS(float, t->zproj), (int64_t)64, t->Mq, c.d, out->projected_z);
     TRY(vt_vq_forward_ctr(WS(float, t->zproj), 64, P->codebook, t->Mq, c.K, c.d, c.vq_mode, c.l2_normalized, c.inv_tau, c.beta, c.codebook_w,
@@ -492,9 +526,32 @@ extern "C" int vt_tokenizer_encode(vtTokenizer* t, const vtTokenizerTensors* P, 
     return VT_OK;
 }
 
+// KL bottleneck: z = in_linear(x) [Mq, 2d] -> vt_kl_forward (mean, sample, eps, loss_kl; bf16 sample into vq_rzpad) -> out_linear(sample)
+extern "C" int vt_tokenizer_encode_kl(vtTokenizer* t, const vtTokenizerTensors* P, const float* video, void* ws,
+                                      const vtTokenizerKLOutputs* out, uint64_t seed, vtStream s) {
+    VT_CHECK_ARG(t && P && video && ws && out, "vt_tokenizer_encode_kl: null pointer");
+    VT_CHECK_ARG(t->kl, "vt_tokenizer_encode_kl: the handle has the VQ bottleneck (vt_tokenizer_create): use vt_tokenizer_encode");
+    VT_CHECK_ARG(out->encoded && out->loss_kl, "vt_tokenizer_encode_kl: encoded/loss_kl outputs are required");
+    t->in_backward = false;
+    const vtTokenizerConfig& c = t->c;
+    const int D = c.D, pd = 2 * c.d;
+    TRY(encode_trunk(t, P, video, ws, out->input_norms, s));
+    if (out->projected_z)
+        hipLaunchKernelGGL(compact_cols_kernel, dim3((t->Mq * pd + 255) / 256), dim3(256), 0, (hipStream_t)s, WS(float, t->zproj), (int64_t)64, t->Mq, pd, out->projected_z);
+    TRY(vt_kl_forward(WS(float, t->zproj), 64, t->Mq, c.d, c.B, seed, t->seed_ctr, out->mean, out->regularized_z, WS(void, t->vq_rzpad), 64,
+                      WS(float, t->kl_noise), out->loss_kl, WS(void, t->kl_ws), s));
+    if (out->noise) TRY(copy_d2d(out->noise, WS(void, t->kl_noise), (size_t)t->Mq * c.d * 4, (hipStream_t)s));
+    vtGemmNT g = nt(t, ws, WS(void, t->vq_rzpad), 64, WS(void, t->out_wb), 64, t->Mq, D, 64, VT_EPI_F32, out->encoded, D);
+    g.bias = P->out_b; g.round_bf16 = 1;
+    TRY(vt_gemm_nt(&g, s));
+    VT_CHECK_LAUNCH("vt_tokenizer_encode_kl");
+    return VT_OK;
+}
+
 extern "C" int vt_tokenizer_codes_to_encoded(vtTokenizer* t, const vtTokenizerTensors* P, const int64_t* indices, void* ws,
                                              float* encoded, vtStream s) {
     VT_CHECK_ARG(t && P && indices && ws && encoded, "vt_tokenizer_codes_to_encoded: null pointer");
+    VT_CHECK_ARG(!t->kl, "vt_tokenizer_codes_to_encoded: the handle has the KL bottleneck (no codebook)");
     t->in_backward = false;
     const vtTokenizerConfig& c = t->c;
     TRY(vt_vq_prep_codebook(P->codebook, c.K, c.d, c.l2_normalized, WS(float, t->vq_E), WS(float, t->vq_wnorm), WS(void, t->vq_ws), s));
@@ -785,15 +842,22 @@ extern "C" int vt_tokenizer_backward(vtTokenizer* t, const vtTokenizerTensors* P
             vtGemmTN w = tn(WS(void, t->dEncb), D, WS(void, t->vq_rzpad), 64, t->Mqp, D, 64, G->out_w, c.d);
             w.q_lim = c.d;
             TRY(skinny_wgrad(t, w, ws, s));
-            // VQ backward: straight-through + commitment to z, codebook loss to the embedding
-            TRY(vt_vq_backward(WS(float, t->d_rz), 64, gscal, c.beta, c.codebook_w, WS(float, t->vq_zn), WS(float, t->vq_znorm), WS(float, t->vq_E),
-                               WS(float, t->vq_wnorm), WS(int64_t, t->vq_idx), t->Mq, c.K, c.d, c.l2_normalized, nullptr, WS(void, t->dz_pad), 64,
-                               c.freeze_codebook ? nullptr : G->codebook, WS(void, t->vq_ws), s));
+            const int pd = t->kl ? 2 * c.d : c.d;   // in_linear outputs
+            if (t->kl) {
+                // KL backward: reparameterised sample + KL term to the interleaved (mean, logvar) columns of z
+                TRY(vt_kl_backward(WS(float, t->d_rz), 64, nullptr, gscal, WS(float, t->zproj), 64, WS(float, t->kl_noise), t->Mq, c.d, c.B, nullptr,
+                                   WS(void, t->dz_pad), 64, s));
+            } else {
+                // VQ backward: straight-through + commitment to z, codebook loss to the embedding
+                TRY(vt_vq_backward(WS(float, t->d_rz), 64, gscal, c.beta, c.codebook_w, WS(float, t->vq_zn), WS(float, t->vq_znorm), WS(float, t->vq_E),
+                                   WS(float, t->vq_wnorm), WS(int64_t, t->vq_idx), t->Mq, c.K, c.d, c.l2_normalized, nullptr, WS(void, t->dz_pad), 64,
+                                   c.freeze_codebook ? nullptr : G->codebook, WS(void, t->vq_ws), s));
+            }
             // in_linear: bias grad, wgrad, dgrad scattered into the last Nq rows of the encoder output gradient
             TRY(vt_colsum(WS(void, t->dz_pad), 1, 64, id, t->Mq, 64, WS(float, t->tmp_vec), WS(void, t->cs_ws), s));
-            TRY(copy_d2d(G->in_b, WS(void, t->tmp_vec), (size_t)c.d * 4, hs));
+            TRY(copy_d2d(G->in_b, WS(void, t->tmp_vec), (size_t)pd * 4, hs));
             w = tn(WS(void, t->dz_pad), 64, WS(void, t->zb), D, t->Mqp, 64, D, G->in_w, D);
-            w.p_lim = c.d;
+            w.p_lim = pd;
             TRY(skinny_wgrad(t, w, ws, s));
             // (the encoder goes on in the rotation of gradient sets where the decoder stopped: with the weight gradients on their own
             // stream, set 0 may still be read by the decoder's last group)

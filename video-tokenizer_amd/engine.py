@@ -48,7 +48,7 @@ def _flat_order(model):
         out.append(("decoder_patch_query_token_type_embed", model.decoder_patch_query_token_type_embed, st))
     named = dict(model.named_parameters())
     bn = model._bt_names   # 'vq': bottleneck.{in,out}_linear.* + bottleneck.regularizer.embedding.weight; 'sq': sq_{in,out}_linear.* + bottleneck.embedding.weight
-    out += [(bn[k], named[bn[k]], st) for k in ("out_b", "out_w", "codebook", "in_b", "in_w")]
+    out += [(bn[k], named[bn[k]], st) for k in ("out_b", "out_w", "codebook", "in_b", "in_w") if bn[k] is not None]   # ('skl': no codebook)
     fc2b("encoder", de - 1, st)
     for k in range(1, de + 1):
         i = de - k
@@ -96,11 +96,13 @@ class _Tensors:
 class _State:
     """One engine handle + workspace for a fixed (batch, frames, size, vq mode) geometry."""
 
-    def __init__(self, engine, key, cfg, device):
+    def __init__(self, engine, key, cfg, device, kl=False):
         self.key = key
         self.cfg = cfg
+        self.kl = kl              # KL bottleneck ('skl'): vt_tokenizer_create_kl / vt_tokenizer_encode_kl
         h = ctypes.c_void_p()
-        hip.check(hip.lib().vt_tokenizer_create(ctypes.byref(cfg), ctypes.byref(h)), "vt_tokenizer_create")
+        create = "vt_tokenizer_create_kl" if kl else "vt_tokenizer_create"
+        hip.check(getattr(hip.lib(), create)(ctypes.byref(cfg), ctypes.byref(h)), create)
         self.handle = h
         nbytes = hip.lib().vt_tokenizer_workspace_bytes(h)
         self.ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
@@ -198,7 +200,8 @@ class TokenizerEngine:
     def state_for(self, B, T, S, device):
         m = self.model
         mode, l2n, inv_tau, beta, cw, frozen = m._vq_engine_cfg()
-        key = (B, T, S, mode, inv_tau, str(device))
+        kl = getattr(m, "_kl", False)
+        key = (B, T, S, "kl" if kl else mode, inv_tau, str(device))
         st = self.states.get(key)
         if st is None:
             c = hip.TokenizerConfig()
@@ -208,7 +211,7 @@ class TokenizerEngine:
             c.vq_mode, c.l2_normalized = mode, int(l2n)
             c.inv_tau, c.beta, c.codebook_w = inv_tau, beta, cw
             c.freeze_codebook = int(frozen)
-            st = _State(self, key, c, device)
+            st = _State(self, key, c, device, kl)
             if self.split_k is not None:
                 hip.check(hip.lib().vt_tokenizer_set_split_k(st.handle, int(self.split_k)), "vt_tokenizer_set_split_k")
             if self.wgrad_tail:
@@ -290,6 +293,16 @@ def _outputs(m, B, device):
     }
 
 
+def _outputs_kl(m, B, device):
+    Nq, D, d = m.bottleneck_token_num, m.decoder_hidden_size, m.bottleneck_dim
+    f = dict(device=device, dtype=torch.float32)
+    return {
+        "encoded": torch.empty(B, Nq, D, **f), "mean": torch.empty(B, Nq, d, **f), "projected_z": torch.empty(B, Nq, 2 * d, **f),
+        "regularized_z": torch.empty(B, Nq, d, **f), "noise": torch.empty(B, Nq, d, **f), "loss_kl": torch.empty(1, **f),
+        "input_norms": torch.empty(2, **f),
+    }
+
+
 def _out_struct(o, pred=None):
     s = hip.TokenizerOutputs()
     s.pred_frames = pred.data_ptr() if pred is not None else None
@@ -313,10 +326,17 @@ def run_encode(engine, x):
     st = engine.state_for(B, T, S, x.device)
     ps = engine.param_struct()
     engine.ensure_packed(st, ps)
-    o = _outputs(m, B, x.device)
-    os_ = _out_struct(o)
-    hip.check(hip.lib().vt_tokenizer_encode(st.handle, ctypes.byref(ps.struct), hip.ptr(x), hip.ptr(st.ws), ctypes.byref(os_),
-                                            engine.next_seed(st), hip.stream()), "vt_tokenizer_encode")
+    if st.kl:
+        o = _outputs_kl(m, B, x.device)
+        os_ = hip.TokenizerKLOutputs(**{k: o[k].data_ptr() for k in hip.KL_OUTPUT_FIELDS})
+        hip.check(hip.lib().vt_tokenizer_encode_kl(st.handle, ctypes.byref(ps.struct), hip.ptr(x), hip.ptr(st.ws), ctypes.byref(os_),
+                                                   engine.next_seed(st), hip.stream()), "vt_tokenizer_encode_kl")
+        m.last_noise = o["noise"]    # eps of this forward (tests follow the device's noise); not a key of the output dict
+    else:
+        o = _outputs(m, B, x.device)
+        os_ = _out_struct(o)
+        hip.check(hip.lib().vt_tokenizer_encode(st.handle, ctypes.byref(ps.struct), hip.ptr(x), hip.ptr(st.ws), ctypes.byref(os_),
+                                                engine.next_seed(st), hip.stream()), "vt_tokenizer_encode")
     st.fwd_id += 1
     return st, ps, o
 
@@ -330,8 +350,9 @@ def run_decode(engine, st, ps, encoded, B, T, S):
 
 
 class TokenizerFunction(torch.autograd.Function):
-    """forward(video) -> (pred_frames, losses[4], + non-differentiable VQ outputs); backward fills
-    the flat gradient buffer through vt_tokenizer_backward and hands views of it to autograd."""
+    """forward(video) -> (pred_frames, losses[4], + non-differentiable VQ outputs) -- with the KL bottleneck (pred_frames, loss_kl[1],
+    encoded, mean, projected_z, regularized_z, input_norms); backward fills the flat gradient buffer through vt_tokenizer_backward
+    (gscal = dL/dlosses or dL/dloss_kl) and hands views of it to autograd."""
 
     @staticmethod
     def forward(ctx, engine, x, *params):
@@ -342,6 +363,10 @@ class TokenizerFunction(torch.autograd.Function):
         ctx.engine, ctx.st, ctx.fwd_id = engine, st, st.fwd_id
         ctx.n_params = len(params)
         ctx.x_shape = x.shape
+        if st.kl:
+            nd = (o["encoded"], o["mean"], o["projected_z"], o["regularized_z"], o["input_norms"])
+            ctx.mark_non_differentiable(*nd)
+            return (pred, o["loss_kl"]) + nd
         nd = (o["encoded"], o["indices"], o["projected_z"], o["unregularized_z"], o["regularized_z"], o["emb"], o["input_norms"])
         ctx.mark_non_differentiable(*nd)
         return (pred, o["losses"]) + nd

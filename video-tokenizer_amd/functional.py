@@ -315,6 +315,27 @@ class VectorQuantize(torch.autograd.Function):
         return dz.reshape(ctx.shp), dW, None, None, None, None, None, None
 
 
+class KLSample(torch.autograd.Function):
+    """SummedKLDivergenceRegularizer.forward (models/bottleneck.py:356-371) on vt_kl_forward / vt_kl_backward: z [B, N, 2d] ->
+    (sample, mean [B, N, d], loss_kl 0-dim, noise [B, N, d]); gradients flow through sample, mean and loss_kl into z, the noise is
+    returned detached."""
+
+    @staticmethod
+    def forward(ctx, z, seed):
+        hip.require_gpu(z)
+        z = z.float().contiguous()
+        mean, sample, noise, loss, _ = hip.kl_forward(z, seed)
+        ctx.save_for_backward(z, noise)
+        ctx.mark_non_differentiable(noise)
+        return sample, mean, loss[0].clone(), noise
+
+    @staticmethod
+    def backward(ctx, g_sample, g_mean, g_loss, _gn):
+        z, noise = ctx.saved_tensors
+        gkl = g_loss.reshape(1) if g_loss is not None else None
+        return hip.kl_backward(z, noise, g_sample, g_mean, gkl), None
+
+
 def codebook_entries(indices, codebook, l2_normalized):
     """get_codebook_entry (bottleneck.py:327-344): rows of the (normalised) codebook; fp32 [*indices.shape, d]"""
     hip.require_gpu(indices, codebook)

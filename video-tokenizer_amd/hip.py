@@ -87,6 +87,8 @@ SIGNATURES = {
                                      c_vp, c_vp, c_vp]),
     "vt_stat_gate_backward": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i32, c_i32, ctypes.POINTER(c_i32), c_i32,
                                       c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "vt_kl_forward": (c_i32, [c_vp, c_i64, c_i64, c_i32, c_i32, c_u64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "vt_kl_backward": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp]),
     "vt_qknorm_rope_fwd": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp]),
     "vt_qknorm_rope_bwd_workspace_bytes": (c_sz, []),
     "vt_qknorm_rope_bwd": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
@@ -152,6 +154,13 @@ class TokenizerOutputs(ctypes.Structure):
     _fields_ = [(n, c_vp) for n in OUTPUT_FIELDS]
 
 
+KL_OUTPUT_FIELDS = ("encoded", "mean", "projected_z", "regularized_z", "noise", "loss_kl", "input_norms")
+
+
+class TokenizerKLOutputs(ctypes.Structure):
+    _fields_ = [(n, c_vp) for n in KL_OUTPUT_FIELDS]
+
+
 _TT = ctypes.POINTER(TokenizerTensors)
 ENGINE_SIGNATURES = {
     "vt_pack_weights_grouped": (c_i32, [ctypes.POINTER(PackJob), c_i32, c_vp]),
@@ -185,6 +194,8 @@ ENGINE_SIGNATURES = {
     "vt_tokenizer_backward": (c_i32, [c_vp, _TT, c_vp, c_vp, c_vp, _TT, c_i32, c_i32, ctypes.POINTER(c_i32), c_vp]),
     "vt_tokenizer_set_data_parallel": (c_i32, [c_vp, c_i32]),
     "vt_tokenizer_backward_until_flush": (c_i32, [c_vp, _TT, c_vp, c_vp, c_vp, _TT, c_i32, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32), c_vp]),
+    "vt_tokenizer_create_kl": (c_i32, [ctypes.POINTER(TokenizerConfig), ctypes.POINTER(c_vp)]),
+    "vt_tokenizer_encode_kl": (c_i32, [c_vp, _TT, c_vp, c_vp, ctypes.POINTER(TokenizerKLOutputs), c_u64, c_vp]),
 }
 
 
@@ -623,6 +634,42 @@ def stat_gate_backward(dcodes, dprobs, dmask, z, mask, probs, u, g, w2, levels, 
                                       _levels(levels or []), int(bool(ste)), ptr(dU), ptr(dz), ptr(dw2), ptr(db2), ptr(ws), stream()),
           "vt_stat_gate_backward")
     return dU, dz, dw2, db2
+
+
+# ---- KL bottleneck 'skl' (csrc/vt_kl.hip) ----
+KL_WORKSPACE_BYTES = 4096    # VT_KL_WORKSPACE_BYTES
+
+
+def kl_forward(z, seed=0, seed_counter=None, ldp=0):
+    """z fp32 [B, N, 2d] (mean, logvar interleaved) -> (mean, sample, noise fp32 [B, N, d], loss_kl fp32 [1], sample_pad bf16 [B*N, ldp]
+    or None when ldp == 0)"""
+    require_gpu(z, seed_counter)
+    assert z.dim() == 3 and z.shape[-1] % 2 == 0 and z.dtype == torch.float32
+    z = z.contiguous()
+    B, N, d = z.shape[0], z.shape[1], z.shape[2] // 2
+    dev = z.device
+    mean, sample, noise = (torch.empty(B, N, d, device=dev) for _ in range(3))
+    loss = torch.empty(1, device=dev)
+    pad = torch.empty(B * N, ldp, device=dev, dtype=torch.bfloat16) if ldp else None
+    ws = _ws(KL_WORKSPACE_BYTES, dev)
+    check(lib().vt_kl_forward(ptr(z), 2 * d, B * N, d, B, int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(seed_counter), ptr(mean), ptr(sample), ptr(pad),
+                              ldp, ptr(noise), ptr(loss), ptr(ws), stream()), "vt_kl_forward")
+    return mean, sample, noise, loss, pad
+
+
+def kl_backward(z, noise, g_sample=None, g_mean=None, gkl=None, ldp=0):
+    """-> dz fp32 [B, N, 2d] (and its bf16 copy [B*N, ldp] when ldp > 0); any gradient may be None (zero)"""
+    require_gpu(z, noise, g_sample, g_mean, gkl)
+    B, N, d = z.shape[0], z.shape[1], z.shape[2] // 2
+    z, noise = z.contiguous(), noise.contiguous()
+    g_sample = g_sample.contiguous().float() if g_sample is not None else None
+    g_mean = g_mean.contiguous().float() if g_mean is not None else None
+    gkl = gkl.contiguous().float().reshape(-1) if gkl is not None else None
+    dz = torch.empty_like(z)
+    pad = torch.empty(B * N, ldp, device=z.device, dtype=torch.bfloat16) if ldp else None
+    check(lib().vt_kl_backward(ptr(g_sample), d, ptr(g_mean), ptr(gkl), ptr(z), 2 * d, ptr(noise), B * N, d, B, ptr(dz), ptr(pad), ldp, stream()),
+          "vt_kl_backward")
+    return (dz, pad) if ldp else dz
 
 
 # ---- glue of the TiTok-style block (csrc/vt_gated.hip) ----

@@ -168,14 +168,17 @@ class LARPTokenizer(nn.Module, LocalPretrainedMixin):
             self.decoder111 = Decoder111(**{{"in_grid": "out_grid", "out_tokens": "in_tokens"}.get(k, k): v for k, v in ma.items()
                                             if k in ("model_size", "patch_size", "in_grid", "out_tokens")})
 
+        # regularizer 'skl' on the 'vq' branch (bottleneck.py:98-101, 347-375): the diagonal-Gaussian KL bottleneck, continuous latents
+        self._kl = bottleneck_type == "vq" and str(bottleneck["args"]["regularizer"]["name"]).lower() == "skl"
+        self.last_noise = None   # eps of the last KL forward (inspection / tests)
         if bottleneck_type == "vq":
             self.bottleneck_dim = bottleneck["args"]["bottleneck_dim"]
             self.bottleneck = registry.make(bottleneck, args={"token_nums": self.bottleneck_token_num, "input_dim": encoder_hidden_size,
                                                               "output_dim": decoder_hidden_size})
-            self.codebook_size = bottleneck["args"]["regularizer"]["args"]["codebook_size"]
-            # parameter names the fused engine binds (engine.py): in/out projection, codebook
+            self.codebook_size = bottleneck["args"]["regularizer"]["args"]["codebook_size"]   # (read for 'skl' too, as the reference does)
+            # parameter names the fused engine binds (engine.py): in/out projection, codebook ('skl': none)
             self._bt_names = {"in_w": "bottleneck.in_linear.weight", "in_b": "bottleneck.in_linear.bias", "out_w": "bottleneck.out_linear.weight",
-                              "out_b": "bottleneck.out_linear.bias", "codebook": "bottleneck.regularizer.embedding.weight"}
+                              "out_b": "bottleneck.out_linear.bias", "codebook": None if self._kl else "bottleneck.regularizer.embedding.weight"}
         elif bottleneck_type == "fsq":
             # larp_tokenizer.py:219-228, 412-418: LayerNorm -> Linear(768, 6) -> FSQ([8, 8, 8, 5, 5, 5]) -> Linear(6, 768); `encode` returns
             # {'encoded'} only (the FSQ indices are dropped there).  Not on the fused engine: forward() composes the sub-modules' own
@@ -278,11 +281,13 @@ class LARPTokenizer(nn.Module, LocalPretrainedMixin):
         return self.final_layer.linear.weight
 
     def set_vq_eval_deterministic(self, deterministic=True):
-        if self.bottleneck_type == "vq":
+        if self.bottleneck_type == "vq" and not self._kl:
             self.bottleneck.regularizer.set_eval_deterministic(deterministic)
 
     def _vq_engine_cfg(self):
         """(index mode, l2_normalized, 1/tau, beta, codebook weight, frozen codebook) for the fused engine"""
+        if self._kl:
+            return 0, False, 1.0, 0.0, 0.0, False     # (not read by a KL handle)
         if self.bottleneck_type == "vq":
             vq = self.bottleneck.regularizer
             return vq.index_mode(), bool(vq.l2_normalized), vq.inv_tau(), float(vq.beta), float(vq.codebook_loss_weight), False
@@ -344,6 +349,15 @@ class LARPTokenizer(nn.Module, LocalPretrainedMixin):
 
     # ------------------------------------------------------------------------------- hot path
     def _bottleneck_dict(self, o):
+        if self._kl:
+            # SummedKLDivergenceRegularizer's keys (bottleneck.py:367-372) after Bottleneck.forward's (:181-188); `dist` is torch glue
+            from .bottleneck import DiagonalGaussianDistribution
+            return {
+                "bottleneck_rep": o["mean"], "projected_z": o["projected_z"],
+                "input_norm_first": o["input_norms"][0], "input_norm_last": o["input_norms"][1],
+                "regularized_z": o["regularized_z"], "dist": DiagonalGaussianDistribution(o["projected_z"], deterministic=False),
+                "loss_kl": o["loss_kl"][0],
+            }
         if self.bottleneck_type == "sq":
             # fsq.py:195-206: loss = beta * mean_n sum_d (sg(q) - z)^2 + mean_n sum_d (q - sg(z))^2 = d * (engine loss_q); only key besides
             # 'encoded' (larp_tokenizer.py:423-428)
@@ -364,6 +378,10 @@ class LARPTokenizer(nn.Module, LocalPretrainedMixin):
         if self._composed:
             enc = self._composed_encode(data)
             return {"pred_frames": self._composed_decode(enc["encoded"]).contiguous(), **enc}
+        if self._kl:
+            pred, loss_kl, encoded, mean, pz, rz, norms = _engine.apply(self._engine, data)
+            o = {"mean": mean, "projected_z": pz, "regularized_z": rz, "input_norms": norms, "loss_kl": loss_kl}
+            return {"pred_frames": pred, "encoded": encoded, **self._bottleneck_dict(o)}
         pred, losses, encoded, idx, pz, uz, rz, emb, norms = _engine.apply(self._engine, data)
         o = {"indices": idx, "projected_z": pz, "input_norms": norms, "unregularized_z": uz, "emb": emb, "regularized_z": rz, "losses": losses}
         if self.bottleneck_type == "sq":
@@ -398,6 +416,8 @@ class LARPTokenizer(nn.Module, LocalPretrainedMixin):
             self.last_indices = o.pop("indices")
             return {"encoded": Linear.apply(o.pop("output"), self.sq_out_linear.weight, self.sq_out_linear.bias), **o}
         o = self.bottleneck(z)
+        if self._kl:
+            self.last_noise = self.bottleneck.regularizer.last_noise
         return {"encoded": o.pop("output"), **o}
 
     def _head_perm(self, device):
@@ -489,6 +509,8 @@ class LARPTokenizer(nn.Module, LocalPretrainedMixin):
         import ctypes
         if not bottleneck_rep.is_cuda:
             raise hip.HipError("LARPTokenizer.decode_from_bottleneck: input is on the CPU; no CPU fallback")
+        if self._kl:                              # 'skl': the representation is the mean; decode = identity -> out_linear -> decode
+            return self.decode(self.bottleneck.decode(bottleneck_rep.contiguous().float()))
         if self._composed:
             from .functional import Linear
             if self.bottleneck_type == "fsq":    # (the reference's FSQ has no .decode; here: indices -> codes -> fsq_out_linear -> decode)
