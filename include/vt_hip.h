@@ -560,6 +560,29 @@ int vt_stack_forward(vtStack* st, const vtBlockTensors* blocks_host, const float
 int vt_stack_backward(vtStack* st, const vtBlockTensors* blocks_host, const float* dy, void* ws, const vtBlockTensors* grads_host,
                       float* dx, int32_t need_wgrad, vtStream stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Rotary position embedding on the plain block stack: `ResidualAttentionBlock1` (models/model_new/base/simpletransformer.py:26-121),
+ * the layer of `autoencoder_convpatchify_simplytransformer` = the timm Block above with apply_rotary_emb (base/rope.py:18-24) on q and k.
+ *   vt_rope_rotate: rotates the q and k column blocks of the packed bf16 attention operand qkv [M, 3D] (row stride ld >= 2D, ld % 8 == 0,
+ *     D = 64 H: head_dim 64 only, columns [q | k | v] as vt_attention_fwd reads them) IN PLACE; columns 2D.. (v) are neither read nor
+ *     written, nor are rows M.. of a padded buffer.  Row m has position m % L (any M, any L).  cos_tab / sin_tab: fp32 [L, 32], the tables
+ *     of vt_qknorm_rope_fwd (real / imaginary part of freqs_cis); pair j of every head is (x[2j], x[2j+1]).  conjugate = 0:
+ *     y = x (cos + i sin), the forward; conjugate = 1: y = x (cos - i sin), the backward of the rotation, applied to dq and dk.  bf16 in,
+ *     fp32 arithmetic, one rounding to bf16 (`.type_as(x)` on the bf16 Linear output under autocast).  qkv and the tables 16-byte aligned.
+ *     Checked on the host: VT_ERR_INVALID + vt_last_error.
+ *   vt_stack_forward_rotary / vt_stack_backward_rotary: vt_stack_forward / vt_stack_backward with the rotation between the qkv GEMM and
+ *     the attention (the saved qkv is the rotated one) and its conjugate on dqkv directly behind the attention backward, before the qkv
+ *     input-gradient GEMM and the queued weight gradient read it.  The tables (device memory, [L, 32] for the stack's L) travel with every
+ *     call and nothing is kept on the handle, so one vtStack serves rotary and plain callers.  cos_tab == sin_tab == NULL is the plain
+ *     stack, bit for bit (vt_stack_forward / vt_stack_backward are exactly that).  Tables given: head_dim must be 64.
+ * ------------------------------------------------------------------------------------------ */
+int vt_rope_rotate(void* qkv, int64_t ld, int64_t M, int32_t L, int32_t H, const float* cos_tab, const float* sin_tab, int32_t conjugate,
+                   vtStream stream);
+int vt_stack_forward_rotary(vtStack* st, const vtBlockTensors* blocks_host, const float* cos_tab, const float* sin_tab, const float* x_in,
+                            void* ws, float* x_out, vtStream stream);
+int vt_stack_backward_rotary(vtStack* st, const vtBlockTensors* blocks_host, const float* cos_tab, const float* sin_tab, const float* dy,
+                             void* ws, const vtBlockTensors* grads_host, float* dx, int32_t need_wgrad, vtStream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,6 +25,9 @@ extern "C" int vt_kl_forward(const float* z, int64_t ldz, int64_t M, int32_t d, 
 extern "C" int vt_kl_backward(const float* g_sample, int64_t ldg, const float* g_mean, const float* gkl, const float* z, int64_t ldz,
                               const float* noise, int64_t M, int32_t d, int32_t batch, float* dz, void* dz_pad_bf16, int64_t ldp,
                               vtStream stream) __attribute__((weak));
+// The same for the rotary pass of the plain block stack (vt_rope.hip): without it vt_stack_forward_rotary / _backward_rotary refuse to run.
+extern "C" int vt_rope_rotate(void* qkv, int64_t ld, int64_t M, int32_t L, int32_t H, const float* cos_tab, const float* sin_tab,
+                              int32_t conjugate, vtStream stream) __attribute__((weak));
 
 static const bool g_no_splitk = [] { const char* e = getenv("VT_GEMM_SPLITK"); return e && strcmp(e, "0") == 0; }();   // A/B switch, read once
 
@@ -420,14 +423,17 @@ static vtGemmNT nt(const vtTokenizer* t, void* ws, const void* A, int64_t lda, c
     return p;
 }
 
-// one timm Block forward: x_in -> x_out (both fp32 [M,D])
-static int block_forward(vtTokenizer* t, const BlockBufs& b, const vtBlockTensors& w, const float* x_in, float* x_out, void* ws, vtStream s) {
+// one timm Block forward: x_in -> x_out (both fp32 [M,D]).  rope_cos / rope_sin (both or neither): q and k are rotated in place behind the
+// qkv GEMM (ResidualAttentionBlock1, simpletransformer.py:46-53), so the saved qkv is the rotated one the attention backward needs.
+static int block_forward(vtTokenizer* t, const BlockBufs& b, const vtBlockTensors& w, const float* x_in, float* x_out, void* ws, vtStream s,
+                         const float* rope_cos = nullptr, const float* rope_sin = nullptr) {
     const vtTokenizerConfig& c = t->c;
     const int M = t->M, D = c.D, D3 = t->D3, D4 = t->D4;
     const vtRowMap id = {0, 0, 0};
     TRY(vt_layernorm_fwd(x_in, id, w.norm1_w, w.norm1_b, 1e-5f, M, D, WS(void, b.h1), WS(float, b.mean1), WS(float, b.rstd1), s));
     vtGemmNT g = nt(t, ws, WS(void, b.h1), D, WS(void, b.qkv_wb), D, M, D3, D, VT_EPI_BF16, WS(void, b.qkv), D3);
     TRY(vt_gemm_nt(&g, s));
+    if (rope_cos) TRY(vt_rope_rotate(WS(void, b.qkv), D3, M, t->L, c.H, rope_cos, rope_sin, 0, s));
     TRY(vt_attention_fwd(WS(void, b.qkv), c.B, t->L, c.H, c.D / c.H, WS(void, b.o), WS(float, b.lse), s));
     g = nt(t, ws, WS(void, b.o), D, WS(void, b.proj_wb), D, M, D, D, VT_EPI_F32, WS(void, b.x_mid), D);
     g.bias = w.proj_b; g.residual = x_in; g.ldr = D;
@@ -682,8 +688,9 @@ static void queue_slab_sum(vtTokenizer* t, const float* part, int nslab, int wid
 // Backward of one block.  In: dX (fp32) and gs[set].dx_out (bf16) hold dL/dx_out.  Out: dX holds dL/dx_in and its bf16
 // copy goes to gs[next set].dx_out.  The four weight-gradient GEMMs are queued (t->pending), not launched.
 // prev_bias_grad: where sum_rows(dL/dx_in) goes (= bias gradient of whatever produced x_in), may be NULL.
+// rope_cos / rope_sin: the block's forward rotated q and k; dq and dk are rotated back (conjugate) before anything reads dqkv.
 static int block_backward(vtTokenizer* t, const BlockBufs& b, const vtBlockTensors& w, const vtBlockTensors& gr, const float* x_in,
-                          float* prev_bias_grad, void* ws, vtStream s) {
+                          float* prev_bias_grad, void* ws, vtStream s, const float* rope_cos = nullptr, const float* rope_sin = nullptr) {
     const vtTokenizerConfig& c = t->c;
     const int M = t->M, Mp = t->Mp, D = c.D, D3 = t->D3, D4 = t->D4;
     const vtRowMap id = {0, 0, 0};
@@ -717,6 +724,7 @@ static int block_backward(vtTokenizer* t, const BlockBufs& b, const vtBlockTenso
     TRY(vt_gemm_nt(&g, s));
     // attention backward
     TRY(attn_bwd(t, ws, WS(void, b.qkv), WS(void, b.o), WS(void, t->dob), WS(float, b.lse), 0, dqkv, s));
+    if (rope_cos) TRY(vt_rope_rotate(dqkv, D3, M, t->L, c.H, rope_cos, rope_sin, 1, s));
     // qkv dgrad
     g = nt(t, ws, dqkv, D3, WS(void, b.qkv_wt), D3, M, D, D3, VT_EPI_BF16, WS(void, t->dh), D);
     TRY(vt_gemm_nt(&g, s));
@@ -969,8 +977,20 @@ extern "C" int vt_stack_init_workspace(vtStack* t, void* ws, vtStream stream) {
     return VT_OK;
 }
 
-extern "C" int vt_stack_forward(vtStack* t, const vtBlockTensors* blocks, const float* x_in, void* ws, float* x_out, vtStream s) {
-    VT_CHECK_ARG(t && blocks && x_in && ws && x_out, "vt_stack_forward: null pointer");
+// cos_tab / sin_tab of the rotary variants: NULL (both) = the plain stack, bit for bit; a rotary stack needs head_dim 64 and vt_rope.hip
+static int check_rotary(const vtTokenizer* t, const float* cos_tab, const float* sin_tab, const char* fn) {
+    VT_CHECK_ARG((cos_tab == nullptr) == (sin_tab == nullptr), "%s: cos_tab and sin_tab must both be given or both be NULL", fn);
+    if (!cos_tab) return VT_OK;
+    VT_CHECK_ARG(vt_rope_rotate != nullptr, "%s: the rotary kernel (vt_rope.hip) is not linked into this library", fn);
+    VT_CHECK_ARG(t->c.D == 64 * t->c.H, "%s: rotary q/k need head_dim 64 (D=%d H=%d)", fn, t->c.D, t->c.H);
+    return VT_OK;
+}
+
+extern "C" int vt_stack_forward_rotary(vtStack* t, const vtBlockTensors* blocks, const float* cos_tab, const float* sin_tab, const float* x_in,
+                                       void* ws, float* x_out, vtStream s) {
+    const char* fn = (cos_tab || sin_tab) ? "vt_stack_forward_rotary" : "vt_stack_forward";
+    VT_CHECK_ARG(t && blocks && x_in && ws && x_out, "%s: null pointer", fn);
+    TRY(check_rotary(t, cos_tab, sin_tab, "vt_stack_forward_rotary"));
     t->in_backward = false;
     const int depth = t->c.depth_enc;
     const size_t bytes = (size_t)t->M * t->c.D * 4;
@@ -978,15 +998,21 @@ extern "C" int vt_stack_forward(vtStack* t, const vtBlockTensors* blocks, const 
     TRY(copy_d2d(WS(void, t->x_enc[0]), x_in, bytes, hs));
     TRY(pack_blocks(t, t->enc, blocks, ws, s));
     for (int i = 0; i < depth; ++i)
-        TRY(block_forward(t, t->enc[i], blocks[i], WS(float, t->x_enc[i]), WS(float, t->x_enc[i + 1]), ws, s));
+        TRY(block_forward(t, t->enc[i], blocks[i], WS(float, t->x_enc[i]), WS(float, t->x_enc[i + 1]), ws, s, cos_tab, sin_tab));
     TRY(copy_d2d(x_out, WS(void, t->x_enc[depth]), bytes, hs));
-    VT_CHECK_LAUNCH("vt_stack_forward");
+    VT_CHECK_LAUNCH(fn);
     return VT_OK;
 }
 
-extern "C" int vt_stack_backward(vtStack* t, const vtBlockTensors* blocks, const float* dy, void* ws, const vtBlockTensors* grads,
-                                 float* dx, int32_t need_wgrad, vtStream s) {
-    VT_CHECK_ARG(t && blocks && dy && ws && grads && dx, "vt_stack_backward: null pointer");
+extern "C" int vt_stack_forward(vtStack* t, const vtBlockTensors* blocks, const float* x_in, void* ws, float* x_out, vtStream s) {
+    return vt_stack_forward_rotary(t, blocks, nullptr, nullptr, x_in, ws, x_out, s);
+}
+
+extern "C" int vt_stack_backward_rotary(vtStack* t, const vtBlockTensors* blocks, const float* cos_tab, const float* sin_tab, const float* dy,
+                                        void* ws, const vtBlockTensors* grads, float* dx, int32_t need_wgrad, vtStream s) {
+    const char* fn = (cos_tab || sin_tab) ? "vt_stack_backward_rotary" : "vt_stack_backward";
+    VT_CHECK_ARG(t && blocks && dy && ws && grads && dx, "%s: null pointer", fn);
+    TRY(check_rotary(t, cos_tab, sin_tab, "vt_stack_backward_rotary"));
     t->in_backward = true;
     const int depth = t->c.depth_enc, D = t->c.D;
     const size_t bytes = (size_t)t->M * D * 4;
@@ -999,7 +1025,7 @@ extern "C" int vt_stack_backward(vtStack* t, const vtBlockTensors* blocks, const
     TRY(vt_cast_rows(dX, id, t->M, D, WS(void, t->gs[0].dx_out), D, s));
     TRY(vt_colsum(dX, 0, D, id, t->M, D, grads[depth - 1].fc2_b, WS(void, t->cs_ws), s));
     for (int i = depth - 1; i >= 0; --i) {
-        TRY(block_backward(t, t->enc[i], blocks[i], grads[i], WS(float, t->x_enc[i]), i > 0 ? grads[i - 1].fc2_b : nullptr, ws, s));
+        TRY(block_backward(t, t->enc[i], blocks[i], grads[i], WS(float, t->x_enc[i]), i > 0 ? grads[i - 1].fc2_b : nullptr, ws, s, cos_tab, sin_tab));
         if (!need_wgrad) {  // frozen stack (generator-side pass through the discriminator): input gradient only
             t->pending.clear();      // (the parameter gradients of a frozen stack are not wanted either: drop the queued reductions)
             t->pending_red.clear();
@@ -1009,6 +1035,11 @@ extern "C" int vt_stack_backward(vtStack* t, const vtBlockTensors* blocks, const
         }
     }
     TRY(copy_d2d(dx, dX, bytes, hs));
-    VT_CHECK_LAUNCH("vt_stack_backward");
+    VT_CHECK_LAUNCH(fn);
     return VT_OK;
+}
+
+extern "C" int vt_stack_backward(vtStack* t, const vtBlockTensors* blocks, const float* dy, void* ws, const vtBlockTensors* grads,
+                                 float* dx, int32_t need_wgrad, vtStream s) {
+    return vt_stack_backward_rotary(t, blocks, nullptr, nullptr, dy, ws, grads, dx, need_wgrad, s);
 }

@@ -92,6 +92,7 @@ SIGNATURES = {
     "vt_qknorm_rope_fwd": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp]),
     "vt_qknorm_rope_bwd_workspace_bytes": (c_sz, []),
     "vt_qknorm_rope_bwd": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "vt_rope_rotate": (c_i32, [c_vp, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp]),
     "vt_sigmoid_gate_fwd": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_vp]),
     "vt_sigmoid_gate_bwd": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp]),
     "vt_geglu_fwd": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i64, c_vp]),
@@ -170,6 +171,8 @@ ENGINE_SIGNATURES = {
     "vt_stack_init_workspace": (c_i32, [c_vp, c_vp, c_vp]),
     "vt_stack_forward": (c_i32, [c_vp, ctypes.POINTER(BlockTensors), c_vp, c_vp, c_vp, c_vp]),
     "vt_stack_backward": (c_i32, [c_vp, ctypes.POINTER(BlockTensors), c_vp, c_vp, ctypes.POINTER(BlockTensors), c_vp, c_i32, c_vp]),
+    "vt_stack_forward_rotary": (c_i32, [c_vp, ctypes.POINTER(BlockTensors), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "vt_stack_backward_rotary": (c_i32, [c_vp, ctypes.POINTER(BlockTensors), c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(BlockTensors), c_vp, c_i32, c_vp]),
     "vt_gated_stack_create": (c_i32, [ctypes.POINTER(GatedStackConfig), ctypes.POINTER(c_vp)]),
     "vt_gated_stack_destroy": (None, [c_vp]),
     "vt_gated_stack_workspace_bytes": (c_sz, [c_vp]),
@@ -682,6 +685,18 @@ def qknorm_rope_fwd(qkvg, L, H, q_w, q_b, k_w, k_b, eps, cos, sin):
     check(lib().vt_qknorm_rope_fwd(ptr(qkvg), M, L, H, ptr(q_w), ptr(q_b), ptr(k_w), ptr(k_b), eps, ptr(cos), ptr(sin), ptr(out), stream()),
           "vt_qknorm_rope_fwd")
     return out
+
+
+def rope_rotate(qkv, L, H, cos, sin, conjugate=False, rows=None):
+    """vt_rope_rotate (csrc/vt_rope.hip): rotates the q and k columns of the packed bf16 [M, 3 * 64 H] operand IN PLACE (the first `rows`
+    rows, default all) by the [L, 32] tables, or by their conjugate; returns qkv"""
+    require_gpu(qkv, cos, sin)
+    assert qkv.dtype == torch.bfloat16 and qkv.dim() == 2 and qkv.stride(1) == 1 and qkv.shape[1] >= 2 * 64 * H
+    assert cos.dtype == torch.float32 and sin.dtype == torch.float32 and cos.is_contiguous() and sin.is_contiguous() and cos.shape == (L, 32) == sin.shape
+    M = qkv.shape[0] if rows is None else rows
+    assert 0 < M <= qkv.shape[0]
+    check(lib().vt_rope_rotate(ptr(qkv), qkv.stride(0), M, L, H, ptr(cos), ptr(sin), int(bool(conjugate)), stream()), "vt_rope_rotate")
+    return qkv
 
 
 def qknorm_rope_bwd(qkvg, dqkv, L, H, q_w, k_w, eps, cos, sin, dqkvg):

@@ -2,7 +2,9 @@
 `autoencoder_large`: models/model_new/autoencoder.py:8-87, 89-170, 589-669; the mask-token variants `autoencoder_mask3`,
 `autoencoder_convpatchify_mask2[_greatfsq]`: :173-416; and `autoencoder_first_token_f256t512 / t768 / t1024a` with
 `Decoder_unify`: :672-913, base/blocks.py:690-787 -- what the f256t* yamls name) on the MI355X kernels.  SURVEY §8f rank 3.
-Not built: `autoencoder_convpatchify_simplytransformer` (a different layer type, base/simpletransformer.py).
+`autoencoder_convpatchify_simplytransformer` (:418-497) has the same frame around a different layer: Encoder3 / Decoder3
+(base/blocks.py:162-288) run `ResidualAttentionBlock1` (base/simpletransformer.py), the plain pre-LN block with rotary q / k and a
+final LayerNorm, on the block-stack engine (functional.RotaryBlockStack -> vt_stack_forward_rotary / vt_stack_backward_rotary).
 
 Same module tree and state-dict keys as the reference (`encoder.proj_in`, `encoder.mask_token`,
 `encoder.model_layers.attn_layer.{i}.{to_qkv,q_norm,k_norm,out_proj}`, `encoder.model_layers.ffd_layer.{i}.{0,1,3}`,
@@ -24,7 +26,7 @@ from torch import nn
 
 from . import hip
 from .fsq import FSQ
-from .functional import Linear as LinearFn, PatchEmbed as PatchEmbedFn, _pad64
+from .functional import LayerNormRows, Linear as LinearFn, PatchEmbed as PatchEmbedFn, _pad64, rotary_block_stack
 from .registry import register
 
 import itertools
@@ -297,6 +299,55 @@ class ResidualAttentionBlock(nn.Module):
         return GatedStack.apply(x, cos, sin, self.heads, tuple(key), *params)
 
 
+class SimpleMlp(nn.Module):
+    """simpletransformer.py:7-24 (parameters; act and the p = 0 dropouts have none)"""
+
+    def __init__(self, dim, hidden):
+        super().__init__()
+        self.fc1 = nn.Linear(dim, hidden)
+        self.fc2 = nn.Linear(hidden, dim)
+
+
+class SimpleAttn(nn.Module):
+    """simpletransformer.py:26-72 (parameters: bias-free qkv, proj)"""
+
+    def __init__(self, dim, heads):
+        super().__init__()
+        self.dim, self.heads, self.head_dim = dim, heads, dim // heads
+        assert self.head_dim == 64, "the rotary kernel is built for head_dim 64 (every reference model size, utils.py:6)"
+        self.qkv = nn.Linear(dim, dim * 3, bias=False)
+        self.proj = nn.Linear(dim, dim)
+
+
+class SimpleBlock(nn.Module):
+    """simpletransformer.py:74-87 (parameters in functional.BLOCK_PARAM_NAMES; the forward is the engine's)"""
+
+    def __init__(self, dim, heads, mlp_ratio=4.0):
+        super().__init__()
+        self.norm1 = nn.LayerNorm(dim)
+        self.attn = SimpleAttn(dim, heads)
+        self.norm2 = nn.LayerNorm(dim)
+        self.mlp = SimpleMlp(dim, int(dim * mlp_ratio))
+
+
+class ResidualAttentionBlock1(nn.Module):
+    """simpletransformer.py:89-121: num_layer pre-LN blocks with rotary q / k, then one LayerNorm.  The blocks run as one engine call
+    per direction; the final LayerNorm is row-wise, so it runs on the rows the caller keeps (`keep`, a slice of the sequence) only."""
+
+    def __init__(self, embed_dim=512, heads=8, mlp_ratio=4, num_layer=2):
+        super().__init__()
+        self.num_layer, self.heads = num_layer, heads
+        self.blocks = nn.ModuleList([SimpleBlock(embed_dim, heads, mlp_ratio) for _ in range(num_layer)])
+        self.norm = nn.LayerNorm(embed_dim)
+
+    def forward(self, x, freqs, keep=None):
+        cos, sin = freqs
+        h = rotary_block_stack(x.float(), self.blocks, self.heads, cos, sin)
+        if keep is not None:
+            h = h[:, keep]
+        return LayerNormRows.apply(h, self.norm.weight, self.norm.bias, self.norm.eps)
+
+
 def init_weights(module):
     """models/model_new/base/utils.py:44-51 (ConvTranspose3d is not an nn.Conv3d subclass: it keeps torch's default init)"""
     if isinstance(module, nn.Linear):
@@ -329,6 +380,8 @@ class Encoder(nn.Module, _RopeMixin):
     """blocks.py:18-82: Conv3d patchify, `out_tokens` scalar mask tokens in FRONT of the patch tokens, layers, first
     out_tokens rows -> Linear(width, token_size)"""
 
+    LAYERS = ResidualAttentionBlock
+
     def __init__(self, model_size="tiny", patch_size=(4, 8, 8), in_channels=3, out_channels=5, in_grid=(16, 128, 128), out_tokens=2048, mask="scalar"):
         super().__init__()
         self.patch_size, self.token_size, self.in_channels, self.out_tokens = tuple(patch_size), out_channels, in_channels, out_tokens
@@ -339,16 +392,28 @@ class Encoder(nn.Module, _RopeMixin):
         self.mask_token = nn.Parameter(self.width ** -0.5 * torch.randn(*_mask_shape(mask, out_tokens, self.width)))
         self.freqs = rope_tables(out_tokens, self.grid, head_dim=self.width // self.heads)
         self._freqs_dev = None
-        self.model_layers = ResidualAttentionBlock(self.width, self.heads, mlp_ratio, self.num_layers)
+        self.model_layers = self.LAYERS(self.width, self.heads, mlp_ratio, self.num_layers)
         self.proj_out = nn.Linear(self.width, self.token_size, bias=True)
         self.apply(init_weights)
+
+    def _layers(self, h, keep):
+        """the layer stack on h, rows `keep` of every sequence back"""
+        return self.model_layers(h, freqs=self._freqs(h.device))[:, keep]
 
     def forward(self, x):
         B = x.shape[0]
         tok = PatchEmbedFn.apply(x, self.proj_in.weight, self.proj_in.bias, None)
         h = torch.cat([self.mask_token.expand(B, self.out_tokens, self.width), tok], dim=1)
-        h = self.model_layers(h, freqs=self._freqs(x.device))
-        return LinearFn.apply(h[:, :self.out_tokens], self.proj_out.weight, self.proj_out.bias)
+        h = self._layers(h, slice(0, self.out_tokens))
+        return LinearFn.apply(h, self.proj_out.weight, self.proj_out.bias)
+
+
+class Encoder3(Encoder):
+    """blocks.py:162-223: Encoder on ResidualAttentionBlock1; its final LayerNorm runs on the out_tokens kept rows"""
+    LAYERS = ResidualAttentionBlock1
+
+    def _layers(self, h, keep):
+        return self.model_layers(h, freqs=self._freqs(h.device), keep=keep)
 
 
 class Encoder111(nn.Module, _RopeMixin):
@@ -392,6 +457,7 @@ class Decoder111(nn.Module, _RopeMixin):
 class Decoder(nn.Module, _RopeMixin):
     """blocks.py:85-149: Linear(token_size, width), grid_size scalar mask tokens BEHIND the latents, layers, last grid_size
     rows -> ConvTranspose3d unpatchify"""
+    LAYERS = ResidualAttentionBlock
 
     def __init__(self, model_size="tiny", patch_size=(4, 8, 8), in_channels=5, out_channels=3, in_tokens=2048, out_grid=(32, 256, 256), mask="scalar"):
         super().__init__()
@@ -405,17 +471,28 @@ class Decoder(nn.Module, _RopeMixin):
         self.mask_token = nn.Parameter(self.width ** -0.5 * torch.randn(*_mask_shape(mask, self.grid_size, self.width)))
         self.freqs = rope_tables(in_tokens, self.grid, head_dim=self.width // self.heads)
         self._freqs_dev = None
-        self.model_layers = ResidualAttentionBlock(self.width, self.heads, mlp_ratio, self.num_layers)
+        self.model_layers = self.LAYERS(self.width, self.heads, mlp_ratio, self.num_layers)
         self.proj_out = nn.ConvTranspose3d(self.width, out_channels, kernel_size=self.patch_size, stride=self.patch_size, bias=True)
         self.apply(init_weights)
+
+    def _layers(self, h, keep):
+        return self.model_layers(h, freqs=self._freqs(h.device))[:, keep]
 
     def forward(self, x):
         B = x.shape[0]
         h = LinearFn.apply(x, self.proj_in.weight, self.proj_in.bias)
         h = torch.cat([h, self.mask_token.expand(B, self.grid_size, self.width)], dim=1)
-        h = self.model_layers(h, freqs=self._freqs(x.device))
+        h = self._layers(h, slice(self.in_tokens, None))
         geom = (B, self.in_channels, self.out_grid[0], self.out_grid[1], self.patch_size[0], self.patch_size[1])
-        return ConvTransposePatch.apply(h[:, self.in_tokens:], self.proj_out.weight, self.proj_out.bias, geom)
+        return ConvTransposePatch.apply(h, self.proj_out.weight, self.proj_out.bias, geom)
+
+
+class Decoder3(Decoder):
+    """blocks.py:226-288: Decoder on ResidualAttentionBlock1; its final LayerNorm runs on the grid rows behind the latents"""
+    LAYERS = ResidualAttentionBlock1
+
+    def _layers(self, h, keep):
+        return self.model_layers(h, freqs=self._freqs(h.device), keep=keep)
 
 
 class DecoderUnify(nn.Module, _RopeMixin):
@@ -517,8 +594,9 @@ register("autoencoder_first_token_f256t1024")(AutoEncoderFirstTokenT1024)
 
 class _AutoEncoderBase(nn.Module):
     """autoencoder.py:9-87 / 90-170 / 590-669: every size keyword of the reference constructor is accepted and ignored (the
-    reference hard-codes the geometry); `_geometry` = dict(in_grid, patch_size, tokens) overrides it for small tests."""
+    reference hard-codes the geometry); `_geometry` = dict(in_grid, patch_size, tokens[, model_size]) overrides it for small tests."""
     MODEL_SIZE, LEVELS, MASK = "small", [8, 8, 8, 5, 5, 5], "scalar"
+    ENCODER, DECODER = Encoder, Decoder
     output_format = "bcthw"
 
     def __init__(self, bottleneck=None, prior_model=None, _geometry=None, **kwargs):
@@ -526,11 +604,12 @@ class _AutoEncoderBase(nn.Module):
         g = dict(in_grid=[16, 128, 128], patch_size=[4, 8, 8], tokens=1024)
         g.update(_geometry or {})
         token_size = len(self.LEVELS)
-        self.encoder = Encoder(model_size=self.MODEL_SIZE, patch_size=g["patch_size"], in_channels=3, out_channels=token_size,
-                               in_grid=g["in_grid"], out_tokens=g["tokens"], mask=self.MASK)
+        size = g.get("model_size", self.MODEL_SIZE)
+        self.encoder = self.ENCODER(model_size=size, patch_size=g["patch_size"], in_channels=3, out_channels=token_size,
+                                    in_grid=g["in_grid"], out_tokens=g["tokens"], mask=self.MASK)
         self.quantize = FSQ(levels=self.LEVELS)
-        self.decoder = Decoder(model_size=self.MODEL_SIZE, patch_size=g["patch_size"], in_channels=token_size, out_channels=3,
-                               in_tokens=g["tokens"], out_grid=g["in_grid"], mask=self.MASK)
+        self.decoder = self.DECODER(model_size=size, patch_size=g["patch_size"], in_channels=token_size, out_channels=3,
+                                    in_tokens=g["tokens"], out_grid=g["in_grid"], mask=self.MASK)
         self.prior_model = None
 
     def encode(self, data, **kwargs):
@@ -545,6 +624,13 @@ class _AutoEncoderBase(nn.Module):
     def forward(self, x):
         x_q, _ = self.encode(x)
         return {"pred_frames": self.decode(x_q)}
+
+
+@register("autoencoder_convpatchify_simplytransformer")
+class AutoEncoderSimpleTransformer(_AutoEncoderBase):
+    """autoencoder.py:418-497: Encoder3 / Decoder3 (`base`: width 768, 12 heads, 12 + 12 blocks), 1024 latent tokens, token size 6"""
+    MODEL_SIZE, LEVELS = "base", [8, 8, 8, 5, 5, 5]
+    ENCODER, DECODER = Encoder3, Decoder3
 
 
 @register("autoencoder_convpatchify")
