@@ -550,7 +550,7 @@ int vt_tokenizer_encode_kl(vtTokenizer* tk, const vtTokenizerTensors* params, co
  * the first one's backward needs its own ws.
  * ------------------------------------------------------------------------------------------ */
 typedef struct { int32_t B, L, D, H, depth; } vtStackConfig;
-typedef struct vtTokenizer vtStack;
+typedef struct vtStack vtStack;
 int vt_stack_create(const vtStackConfig* cfg, vtStack** out);
 void vt_stack_destroy(vtStack* st);
 size_t vt_stack_workspace_bytes(const vtStack* st);

@@ -37,6 +37,16 @@ void vt_set_error(const char* fmt, ...);
         }                                                                  \
     } while (0)
 
+// ---- host-side helpers of the two engines (vt_engine.hip, vt_gated_engine.hip) ----
+#define TRY(x)                 \
+    do {                       \
+        int rc__ = (x);        \
+        if (rc__) return rc__; \
+    } while (0)
+#define WS(T, off) ((T*)((char*)ws + (off)))   // typed pointer into the workspace `ws` of the enclosing function
+// (vt_vq.hip still has an int overload of its own for its kernel-launch arithmetic: call either with both arguments of one type)
+static inline size_t round_up(size_t a, size_t b) { return (a + b - 1) / b * b; }
+
 // ---- device helpers ----
 #if defined(__HIP_DEVICE_COMPILE__) || defined(__HIPCC__)
 

@@ -9,15 +9,6 @@
 
 #include "vt_common.h"
 
-#define TRY(x)                  \
-    do {                        \
-        int rc__ = (x);         \
-        if (rc__) return rc__;  \
-    } while (0)
-#define WS(T, off) ((T*)((char*)ws + (off)))
-
-static inline size_t up(size_t a, size_t b) { return (a + b - 1) / b * b; }
-
 struct GLayerBufs {
     // bf16 operand copies of the weights: [N, K] for the forward, [K, N] for the input gradients
     size_t qkv_wb, qkv_wt, out_wb, out_wt, fc1_wb, fc1_wt, fc2_wb, fc2_wt;
@@ -46,10 +37,10 @@ extern "C" int vt_gated_stack_create(const vtGatedStackConfig* cfg, vtGatedStack
     vtGatedStack* t = new vtGatedStack();
     t->c = c;
     t->M = c.B * c.L;
-    t->ipad = (int)up(c.inner, 64);
+    t->ipad = (int)round_up(c.inner, 64);
     const size_t M = t->M, D = c.D, I2 = 2 * (size_t)c.inner, ip = t->ipad;
     size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += up(bytes, 256); return o; };
+    auto take = [&](size_t bytes) { size_t o = off; off += round_up(bytes, 256); return o; };
     t->L.resize(c.depth);
     for (auto& l : t->L) {
         l.qkv_wb = take(4 * D * D * 2); l.qkv_wt = take(D * 4 * D * 2);

@@ -72,27 +72,36 @@ def _block_array(tensors, depth):
 
 class BlockStack(torch.autograd.Function):
     """depth x timm Block(dim, heads, mlp_ratio=4, qkv_bias=False) on x fp32 [B, L, D]; head_dim 64 or 32, any L.
-    One vt_stack_forward / vt_stack_backward call each: the C++ engine enqueues the tokenizer's own block sequence
+    One vt_stack_forward_rotary / vt_stack_backward_rotary call each: the C++ engine enqueues the tokenizer's own block sequence
     (8 launches per block forward, 13 backward + one grouped weight-gradient launch per 4 blocks; reference: timm Block
     as built at models/transformer.py:18-25, 52-59).  Frozen parameters (requires_grad False everywhere: the
-    generator-side pass through the discriminator) skip the weight-gradient GEMMs."""
+    generator-side pass through the discriminator) skip the weight-gradient GEMMs.
+    cos = sin = None is that plain stack.  cos / sin given (fp32 [L, 32] device tables, titok.rope_tables; head_dim 64): rotary position
+    embedding on q and k, depth x Block of `ResidualAttentionBlock1` (models/model_new/base/simpletransformer.py:74-87): the same
+    launch sequence plus one vt_rope_rotate per block and direction.  The tables travel with the call, so both kinds share the
+    handles and the workspace pool."""
 
     @staticmethod
-    def forward(ctx, x, n_head, *params):
-        hip.require_gpu(x, *params)
+    def forward(ctx, x, cos, sin, n_head, *params):
+        hip.require_gpu(x, cos, sin, *params)
         assert x.dim() == 3 and x.dtype == torch.float32
         B, L, D = x.shape
         depth = len(params) // PARAMS_PER_BLOCK
         assert depth * PARAMS_PER_BLOCK == len(params) and D % n_head == 0
+        if cos is not None:
+            assert D == 64 * n_head
+            assert cos.dtype == torch.float32 and sin.dtype == torch.float32 and cos.shape == (L, 32) == sin.shape
+            cos, sin = cos.contiguous(), sin.contiguous()
         key = (B, L, D, n_head, depth)
         handle, nbytes = _stack(key)
         params = tuple(p_.detach().float().contiguous() for p_ in params)
         ws = _take_ws(key, nbytes, x.device)
         xin = x.contiguous()
         out = torch.empty_like(xin)
-        hip.check(hip.lib().vt_stack_forward(handle, _block_array(params, depth), hip.ptr(xin), hip.ptr(ws), hip.ptr(out), hip.stream()), "vt_stack_forward")
+        hip.check(hip.lib().vt_stack_forward_rotary(handle, _block_array(params, depth), hip.ptr(cos), hip.ptr(sin), hip.ptr(xin), hip.ptr(ws),
+                                                    hip.ptr(out), hip.stream()), "vt_stack_forward_rotary")
         if any(ctx.needs_input_grad):     # a backward may follow: the activations stay in ws until then
-            ctx.key, ctx.ws, ctx.params, ctx.done = key, ws, params, False
+            ctx.key, ctx.ws, ctx.params, ctx.tabs, ctx.done = key, ws, params, (cos, sin), False
         else:                             # inference: the workspace is free again behind this forward (stream order)
             _WS_POOL[(key, str(x.device))].append(ws)
         return out
@@ -103,59 +112,8 @@ class BlockStack(torch.autograd.Function):
             raise RuntimeError("BlockStack: second backward through the same forward (its workspace was recycled)")
         B, L, D, H, depth = ctx.key
         handle, _ = _stack(ctx.key)
-        need = ctx.needs_input_grad[2:]
-        grads = [torch.empty_like(p_) for p_ in ctx.params]     # LayerNorm / bias gradients are always produced
-        dx = torch.empty(B, L, D, device=dy.device, dtype=torch.float32)
-        dyc = dy.contiguous().float()
-        hip.check(hip.lib().vt_stack_backward(handle, _block_array(ctx.params, depth), hip.ptr(dyc), hip.ptr(ctx.ws), _block_array(grads, depth),
-                                              hip.ptr(dx), int(any(need)), hip.stream()), "vt_stack_backward")
-        ctx.done = True
-        _WS_POOL[(ctx.key, str(dy.device))].append(ctx.ws)
-        ctx.ws = None
-        return (dx, None, *[g if n else None for g, n in zip(grads, need)])
-
-
-def block_stack(x, blocks, n_head):
-    return BlockStack.apply(x, n_head, *block_params(blocks))
-
-
-class RotaryBlockStack(torch.autograd.Function):
-    """BlockStack with rotary position embedding on q and k: depth x Block of `ResidualAttentionBlock1`
-    (models/model_new/base/simpletransformer.py:74-87) on x fp32 [B, L, D], head_dim 64, any L.  cos / sin: fp32 [L, 32] device tables
-    (titok.rope_tables).  One vt_stack_forward_rotary / vt_stack_backward_rotary call each: BlockStack's launch sequence plus one
-    vt_rope_rotate per block and direction.  The handle and the workspace pool are BlockStack's (the tables travel with the call)."""
-
-    @staticmethod
-    def forward(ctx, x, cos, sin, n_head, *params):
-        hip.require_gpu(x, cos, sin, *params)
-        assert x.dim() == 3 and x.dtype == torch.float32
-        B, L, D = x.shape
-        depth = len(params) // PARAMS_PER_BLOCK
-        assert depth * PARAMS_PER_BLOCK == len(params) and D == 64 * n_head
-        assert cos.dtype == torch.float32 and sin.dtype == torch.float32 and cos.shape == (L, 32) == sin.shape
-        cos, sin = cos.contiguous(), sin.contiguous()
-        key = (B, L, D, n_head, depth)
-        handle, nbytes = _stack(key)
-        params = tuple(p_.detach().float().contiguous() for p_ in params)
-        ws = _take_ws(key, nbytes, x.device)
-        xin = x.contiguous()
-        out = torch.empty_like(xin)
-        hip.check(hip.lib().vt_stack_forward_rotary(handle, _block_array(params, depth), hip.ptr(cos), hip.ptr(sin), hip.ptr(xin), hip.ptr(ws),
-                                                    hip.ptr(out), hip.stream()), "vt_stack_forward_rotary")
-        if any(ctx.needs_input_grad):
-            ctx.key, ctx.ws, ctx.params, ctx.tabs, ctx.done = key, ws, params, (cos, sin), False
-        else:
-            _WS_POOL[(key, str(x.device))].append(ws)
-        return out
-
-    @staticmethod
-    def backward(ctx, dy):
-        if ctx.done:
-            raise RuntimeError("RotaryBlockStack: second backward through the same forward (its workspace was recycled)")
-        B, L, D, H, depth = ctx.key
-        handle, _ = _stack(ctx.key)
         need = ctx.needs_input_grad[4:]
-        grads = [torch.empty_like(p_) for p_ in ctx.params]
+        grads = [torch.empty_like(p_) for p_ in ctx.params]     # LayerNorm / bias gradients are always produced
         dx = torch.empty(B, L, D, device=dy.device, dtype=torch.float32)
         dyc = dy.contiguous().float()
         cos, sin = ctx.tabs
@@ -167,8 +125,12 @@ class RotaryBlockStack(torch.autograd.Function):
         return (dx, None, None, None, *[g if n else None for g, n in zip(grads, need)])
 
 
+def block_stack(x, blocks, n_head):
+    return BlockStack.apply(x, None, None, n_head, *block_params(blocks))
+
+
 def rotary_block_stack(x, blocks, n_head, cos, sin):
-    return RotaryBlockStack.apply(x, cos, sin, n_head, *block_params(blocks))
+    return BlockStack.apply(x, cos, sin, n_head, *block_params(blocks))
 
 
 # ------------------------------------------------------------------------------------------------------------------------

@@ -4,7 +4,7 @@
 `Decoder_unify`: :672-913, base/blocks.py:690-787 -- what the f256t* yamls name) on the MI355X kernels.  SURVEY §8f rank 3.
 `autoencoder_convpatchify_simplytransformer` (:418-497) has the same frame around a different layer: Encoder3 / Decoder3
 (base/blocks.py:162-288) run `ResidualAttentionBlock1` (base/simpletransformer.py), the plain pre-LN block with rotary q / k and a
-final LayerNorm, on the block-stack engine (functional.RotaryBlockStack -> vt_stack_forward_rotary / vt_stack_backward_rotary).
+final LayerNorm, on the block-stack engine (functional.rotary_block_stack -> vt_stack_forward_rotary / vt_stack_backward_rotary).
 
 Same module tree and state-dict keys as the reference (`encoder.proj_in`, `encoder.mask_token`,
 `encoder.model_layers.attn_layer.{i}.{to_qkv,q_norm,k_norm,out_proj}`, `encoder.model_layers.ffd_layer.{i}.{0,1,3}`,
