@@ -340,11 +340,11 @@ def layernorm_fwd(x, gamma, beta, eps, rows=None, xmap=None, y=None):
     return y, mean, rstd
 
 
-def layernorm_bwd(dy, x, gamma, mean, rstd, dres=None, xmap=None, dx=None, dxb=None, want_dxsum=True):
+def layernorm_bwd(dy, x, gamma, mean, rstd, dres=None, xmap=None, dx=None, dxb=None, want_dxsum=True, want_dxb=True):
     rows, dim = dy.shape
     dev = x.device
     dx = torch.empty_like(x) if dx is None else dx
-    dxb = torch.empty(x.shape, device=dev, dtype=torch.bfloat16) if dxb is None else dxb
+    dxb = torch.empty(x.shape, device=dev, dtype=torch.bfloat16) if dxb is None and want_dxb else dxb
     dg, db = torch.empty(dim, device=dev), torch.empty(dim, device=dev)
     ds = torch.empty(dim, device=dev) if want_dxsum else None
     ws = _ws(lib().vt_layernorm_bwd_workspace_bytes(dim), dev)
@@ -381,6 +381,30 @@ def cast_rows(src, rows=None, rmap=None, ldd=None, dst=None):
 
 def assemble_rows(dst, seq, off, batch, n, src=None, table=None, vec=None):
     check(lib().vt_assemble_rows(ptr(dst), seq, off, batch, n, dst.shape[-1], ptr(src), ptr(table), ptr(vec), stream()), "vt_assemble_rows")
+
+
+def zero_rows(a=None, b=None, rows=None, rmap=None):
+    """zeroes rows rmap(r), r < rows, of the fp32 matrix `a` [*, dim] and / or its bf16 twin `b`, in place"""
+    require_gpu(a, b)
+    t = a if a is not None else b
+    dim = t.shape[-1]
+    rows = rows if rows is not None else t.numel() // dim
+    check(lib().vt_zero_rows(ptr(a), ptr(b), rmap or IDENT, rows, dim, stream()), "vt_zero_rows")
+
+
+def sum_slabs(slabs, nslab, width, slab_stride=None):
+    """out[c] = sum_s slabs[s * slab_stride + c] (fp32, fixed order); slab_stride defaults to width (dense slabs)"""
+    require_gpu(slabs)
+    out = torch.empty(width, device=slabs.device, dtype=torch.float32)
+    check(lib().vt_sum_slabs(ptr(slabs), nslab, slab_stride or width, width, ptr(out), stream()), "vt_sum_slabs")
+    return out
+
+
+def scale_rows(src, scale, dst=None, dstb=None):
+    """dst = scale * src (fp32; dst may be src) and / or dstb = its bf16 copy; at least one of the two"""
+    require_gpu(src, dst, dstb)
+    dim = src.shape[-1]
+    check(lib().vt_scale_rows(ptr(src), scale, src.numel() // dim, dim, ptr(dst), ptr(dstb), stream()), "vt_scale_rows")
 
 
 def pack_weight(w, row_perm=None, want_t=True, ldd=None, lddT=None, n_pad=None, k_pad=None):
