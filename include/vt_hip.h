@@ -82,13 +82,19 @@ typedef struct {
                                                 layer i of models/model_new/base/transformer.py:88-90 -- before out / out2 are written */
     int32_t tile;                            /* tile generation for THIS call: 0 = automatic (use this; 192x192x64 tiles on a
                                                 3-stage LDS-DMA ring, one persistent workgroup per CU, when the problem fills
-                                                them, else 128x128x64).  Tests / tuning: 1 = force 128, 2 = force 192, 5 = 192x96
-                                                two workgroups per CU, 6 = 192x192 one tile per workgroup, 7 = the M <= 64
-                                                weight-streaming kernel, 8..15 = 192x192 with every other CU starting 1..8 us late
-                                                (timing experiment, correct results), 3/4/17/18 = timing ablations with WRONG results, 19 = 192x192 walking its
-                                                tiles as a row-major list, 19 + W (W = 1..12) = in column blocks of W tile columns (automatic: 6 or 8 when N spans
-                                                at least 6 tiles, else row-major; A/B timing of the order, same results).  Results do not depend on the choice (same fp32
-                                                summation order) unless K is split, below.  The library keeps no such setting between calls */
+                                                them, else 128x128x64).  Tests / tuning: 1 = force 128 (2-deep ring), 16 = force 128
+                                                (4-deep ring), 2 = force 192, 5 = 192x96 two workgroups per CU, 6 = 192x192 one tile per
+                                                workgroup, 7 = the M <= 64 weight-streaming kernel, 19 = 192x192 walking its tiles as a
+                                                row-major list, 19 + W (W = 1..12) = in column blocks of W tile columns (A/B timing of the
+                                                order, same results).  Every other value is VT_ERR_INVALID: 3, 4, 8..15, 17 and 18 once
+                                                selected timing experiments inside the 192x192 kernel (some with wrong results on purpose);
+                                                they are gone, and no caller passed them.  Results do not depend on the choice (same fp32
+                                                summation order) unless K is split, below.  The library keeps no such setting between calls.
+                                                Automatic tile order of both NT kernels (vt_auto_col_block): column blocks of the width
+                                                nearest the square root of the tiles one XCD has in flight, the tile columns cut into
+                                                near-equal blocks; the row-major list when one block would span the matrix.
+                                                VT_GEMM_TILE_ORDER=W in the environment (read once per process) forces W, as 19 + W does
+                                                per call, for every NT launch of either kernel: whole-step A/B timing */
     void* splitk_ws; int64_t splitk_ws_bytes; /* optional workspace of vt_gemm_nt_splitk_workspace_bytes() bytes, 256-byte aligned, ZERO when first
                                                 handed over (its first 4 KiB are arrival counters the kernel returns to zero) and used by one stream
                                                 at a time.  With it, a launch of the 128x128 kernel that would leave most CUs idle (the N = 768

@@ -329,6 +329,22 @@ def test_c_abi_exports_every_declared_symbol():
     assert lib.vt_tokenizer_create(ctypes.byref(cfg), ctypes.byref(h)) == -1
 
 
+def test_gemm_nt_rejects_the_removed_tile_values():
+    """vtGemmNT.tile 3, 4, 8..15, 17 and 18 selected timing experiments that are gone: with otherwise valid arguments they are refused by the
+    host-side validation (no launch, no GPU), and the message names the field."""
+    lib = vt.hip.lib()
+    p = vt.hip.GemmNT()
+    p.A = p.B = p.out = 4096                   # non-null, 16-byte aligned, never dereferenced
+    p.M, p.N, p.K, p.lda, p.ldb, p.ldo = 192, 192, 64, 64, 64, 192
+    p.epi, p.splitk = vt.hip.EPI_BF16, 1
+    buf = ctypes.create_string_buffer(512)
+    for tile in (3, 4, 8, 15, 17, 18):
+        p.tile = tile
+        assert lib.vt_gemm_nt(ctypes.byref(p), None) == -1, tile
+        lib.vt_last_error(buf, 512)
+        assert b"tile %d" % tile in buf.value, buf.value
+
+
 def test_engine_plan_sizes_host_only():
     """vt_tokenizer_create / workspace_bytes are pure host planning: config B at 8 clips/GPU fits easily in 288 GB."""
     lib = vt.hip.lib()

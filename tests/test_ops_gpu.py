@@ -400,14 +400,8 @@ def test_gemm_nt_split_k_hand_off_under_uneven_concurrent_load(hip):
         assert int(ws[:4096].view(torch.int32).abs().sum()) == 0
 
 
-@pytest.mark.gpu
-def test_gemm_nt192_gelu_table_equals_the_arithmetic_on_every_bf16_magnitude(hip):
-    """The 192x192 kernel's fc1 epilogue looks gelu(u) up in an LDS table of the bf16 patterns with |u| in [2^-16, 16) and falls back to
-    the arithmetic for a 4-column group that holds anything else; the 128x128 kernel keeps the arithmetic.  B = identity rows, so u is
-    exactly A: every bf16 exponent from 2^-40 to 2^20 in both signs, zeros, and the table's edge patterns land in the epilogue --
-    gelu(u) of the two kernels must be bit-identical (and u itself too)."""
-    import numpy as np
-    M, K = 384, 192
+def _every_bf16_magnitude(M, K):
+    """[M, K] bf16: every exponent from 2^-40 to 2^20 in both signs, zeros, the GELU table's edge patterns, rows that stay inside the table"""
     rng = np.random.default_rng(5)
     exps = rng.integers(-40, 21, size=(M, K))
     vals = np.ldexp(1.0 + rng.integers(0, 128, size=(M, K)) / 128.0, exps) * rng.choice([-1.0, 1.0], size=(M, K))
@@ -415,7 +409,17 @@ def test_gemm_nt192_gelu_table_equals_the_arithmetic_on_every_bf16_magnitude(hip
     vals[1::7, ::5] = -0.0
     vals[0, :8] = [2.0 ** -16, -2.0 ** -16, 2.0 ** -17 * 1.9921875, 15.9375, -15.9375, 16.0, -16.0, 2.0 ** -16 * 1.0078125]   # the table's edges
     vals[2:6] = rng.normal(size=(4, K))          # rows that stay inside the table
-    a = torch.from_numpy(vals.astype(np.float32)).to(torch.bfloat16).cuda()
+    return torch.from_numpy(vals.astype(np.float32)).to(torch.bfloat16).cuda()
+
+
+@pytest.mark.gpu
+def test_gemm_nt192_gelu_table_equals_the_arithmetic_on_every_bf16_magnitude(hip):
+    """The 192x192 kernel's fc1 epilogue looks gelu(u) up in an LDS table of the bf16 patterns with |u| in [2^-16, 16) and falls back to
+    the arithmetic for a 4-column group that holds anything else; the 128x128 kernel keeps the arithmetic.  B = identity rows, so u is
+    exactly A: every bf16 exponent from 2^-40 to 2^20 in both signs, zeros, and the table's edge patterns land in the epilogue --
+    gelu(u) of the two kernels must be bit-identical (and u itself too)."""
+    M, K = 384, 192
+    a = _every_bf16_magnitude(M, K)
     b = torch.eye(K, dtype=torch.bfloat16).cuda()
     u128, g128 = hip.gemm_nt(a, b, epi=hip.EPI_BF16_GELU, tile=1, splitk=1)
     u192, g192 = hip.gemm_nt(a, b, epi=hip.EPI_BF16_GELU, tile=2)
@@ -425,6 +429,48 @@ def test_gemm_nt192_gelu_table_equals_the_arithmetic_on_every_bf16_magnitude(hip
     ref = torch.nn.functional.gelu(a.float()).to(torch.bfloat16)
     # against torch: one bf16 rounding step, plus the arithmetic's own absolute error (Abramowitz-Stegun 7.1.26: 1.5e-7 on erf, times |u|)
     assert ((g192.float() - ref.float()).abs() <= 2.0 ** -7 * ref.float().abs() + 4e-7 * a.float().abs().clamp(min=1.0)).all()
+
+
+@pytest.mark.gpu
+def test_gemm_nt192_gelu_table_on_the_8_byte_read_back_equals_the_arithmetic(hip):
+    """N = 196 is no multiple of 8, so the 192x192 kernel reads its staged image back 8 bytes (4 columns) per lane and looks gelu(u) up
+    four values at a time; the same inputs as above (B = 196 x 192 identity rows, the last 4 columns of u are zero): u and gelu(u) must
+    be bit-identical to the 128x128 kernel's arithmetic."""
+    M, K, N = 384, 192, 196
+    a = _every_bf16_magnitude(M, K)
+    b = torch.eye(N, K, dtype=torch.bfloat16).cuda()
+    u128, g128 = hip.gemm_nt(a, b, epi=hip.EPI_BF16_GELU, tile=1, splitk=1)
+    u192, g192 = hip.gemm_nt(a, b, epi=hip.EPI_BF16_GELU, tile=2)
+    torch.cuda.synchronize()
+    assert torch.equal(u192[:, :K], a)
+    assert torch.equal(u192, u128)
+    assert torch.equal(g192.view(torch.int16), g128.view(torch.int16))
+
+
+@pytest.mark.gpu
+def test_gemm_nt192_f32_row_map_crosses_a_group_boundary_inside_a_tile(hip):
+    """The 192x192 kernel's fp32 epilogue finds the output row of a tile row without a division when the row map's groups are at least a
+    tile long: groups of 200 rows over M = 400, so tile rows 192..383 cross from group 0 into group 1.  Small integers (exact in fp32):
+    mapped rows equal A B^T + residual exactly, every other row keeps its sentinel, and the 128x128 kernel (one division per row) agrees."""
+    M, N, K, grp, stride, off = 400, 192, 64, 200, 260, 30
+    g = torch.Generator().manual_seed(17)
+    A = torch.randint(-3, 4, (M, K), generator=g).float()
+    B = torch.randint(-3, 4, (N, K), generator=g).float()
+    rows_out = (M // grp) * stride
+    res = torch.randint(-50, 51, (rows_out, N), generator=g).float()
+    ref = torch.full((rows_out, N), -12345.0)
+    for q in range(M // grp):
+        rows = slice(q * stride + off, q * stride + off + grp)
+        ref[rows] = A[q * grp:(q + 1) * grp] @ B.t() + res[rows]
+    got = {}
+    for tile in (2, 1):
+        out = torch.full((rows_out, N), -12345.0, device="cuda")
+        hip.gemm_nt(A.to(torch.bfloat16).cuda(), B.to(torch.bfloat16).cuda(), hip.EPI_F32, out=out, residual=res.cuda(),
+                    omap=hip.RowMap(grp, stride, off), tile=tile)
+        torch.cuda.synchronize()
+        got[tile] = out.cpu()
+    assert torch.equal(got[2], ref)
+    assert torch.equal(got[1], got[2])
 
 
 # -------------------------------------------------------------------------------------- attention

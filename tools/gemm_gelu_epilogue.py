@@ -16,11 +16,6 @@ cs = torch.empty((M + 191) // 192, 4 * D, device="cuda")
 cases = {"plain bf16": dict(epi=hip.EPI_BF16, bias=bias, out=out),
          "fc1 GELU": dict(epi=hip.EPI_BF16_GELU, bias=bias, out=out, out2=out2),
          "fc2-dgrad DGELU": dict(epi=hip.EPI_BF16_DGELU, aux=u, out=out, colsum_partial=cs),
-         # timing ablations (wrong results): where does the epilogue's time go?
-         "plain, no stores": dict(epi=hip.EPI_BF16, bias=bias, out=out, tile=17),
-         "plain, stores stay in cache": dict(epi=hip.EPI_BF16, bias=bias, out=out, tile=18),
-         "GELU, no stores / no gelu": dict(epi=hip.EPI_BF16_GELU, bias=bias, out=out, out2=out2, tile=17),
-         "GELU, stores stay in cache": dict(epi=hip.EPI_BF16_GELU, bias=bias, out=out, out2=out2, tile=18),
          "plain, one tile per WG": dict(epi=hip.EPI_BF16, bias=bias, out=out, tile=6)}
 res = {}
 for _ in range(5):

@@ -13,7 +13,6 @@
 //
 // The MFMA is issued as D' = B_frag x A_frag so that one lane ends up with FOUR CONSECUTIVE OUTPUT
 // COLUMNS of one output row (16 B of fp32 / 8 B of bf16 per store) instead of four rows.
-#include <cstdlib>
 #include "vt_common.h"
 #include "vt_gemm_epilogue.h"
 
@@ -448,25 +447,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const TNArgs a) {
         __syncthreads();
     }
 
-    // acc[i][j][r] = C[p0 + wr*64 + i*16 + (lane&15)][q0 + wc*64 + j*16 + (lane>>4)*4 + r]
-    const int fr = lane & 15, fq = lane >> 4;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int pr = p0 + wr * 64 + i * 16 + fr;
-        if (pr >= p.p_lim) continue;
-        const int64_t orow = p.row_perm ? (int64_t)p.row_perm[pr] : (int64_t)pr;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int qc = q0 + wc * 64 + j * 16 + fq * 4;
-            if (qc >= p.q_lim) continue;
-            float* o = p.out + orow * p.ldo + qc;
-            if (qc + 3 < p.q_lim && ((p.ldo & 3) == 0)) {
-                *(f32x4*)o = acc[i][j];
-            } else {
-                for (int r = 0; r < 4 && qc + r < p.q_lim; ++r) o[r] = acc[i][j][r];
-            }
-        }
-    }
+    tn_store_acc(p, acc, p0 + wr * 64, q0 + wc * 64, lane);
 }
 
 // ------------------------------------------------------------------------------------------------ skinny NT (M <= 64)
@@ -544,14 +525,41 @@ static void launch_skinny(const vtGemmNT& p, hipStream_t s) {
 constexpr int VT_SPLITK_CTR_BYTES = 4096;   // arrival counters (one per 128x128 output tile) in front of the partial sums
 extern "C" size_t vt_gemm_nt_splitk_workspace_bytes(void) { return VT_SPLITK_CTR_BYTES + (size_t)512 * BM * BN * 4; }   // automatic rule: tiles x split <= 2 x 256
 
-int vt_gemm_nt192_launch(const vtGemmNT& p, hipStream_t s, int dbg, int half, int one_tile, int order);
+// vt_gemm192.hip
+int vt_gemm_nt192_launch(const vtGemmNT& p, hipStream_t s, int half, int one_tile, int order);
 int vt_gemm_tn192_launch(const vtGemmTN* ph, int n, hipStream_t s, int burst);
 int vt_gemm192_init();
+int vt_gemm_num_cus();
+int vt_gemm_col_block(int forced, int tiles_n, int nwg, int wg_per_cu);
+
+// What a value of vtGemmNT.tile asks for
+struct NTTile {
+    enum Kernel { AUTO, SKINNY, T128_RING2, T128_RING4, T192, T192X96 } kernel;
+    bool one_tile;   // 192x192 only: one tile per workgroup instead of the persistent walk
+    int order;       // 192x192 only: forced tile order (0 = row-major list, W = column blocks of W tile columns), -1 = automatic
+};
+static bool decode_nt_tile(int tile, NTTile& t) {
+    t = NTTile{NTTile::AUTO, false, -1};
+    switch (tile) {
+        case 0: return true;
+        case 1: t.kernel = NTTile::T128_RING2; return true;
+        case 2: t.kernel = NTTile::T192; return true;
+        case 5: t.kernel = NTTile::T192X96; return true;
+        case 6: t.kernel = NTTile::T192; t.one_tile = true; return true;
+        case 7: t.kernel = NTTile::SKINNY; return true;
+        case 16: t.kernel = NTTile::T128_RING4; return true;
+        default:
+            if (tile < 19 || tile > 31) return false;
+            t.kernel = NTTile::T192; t.order = tile - 19;
+            return true;
+    }
+}
+
 extern "C" int vt_gemm_nt(const vtGemmNT* ph, vtStream stream) {
     const vtGemmNT& p = *ph;
     VT_CHECK_ARG(p.A && p.B && p.out, "vt_gemm_nt: null operand");
-    const int g_gemm_variant = p.tile;   // per call (vtGemmNT.tile); the library holds no tile setting of its own
-    VT_CHECK_ARG(g_gemm_variant >= 0 && g_gemm_variant <= 31, "vt_gemm_nt: tile %d (0 auto, 1 = 128x128 2-deep ring, 16 = 128x128 4-deep ring, 2 = 192x192, 5 = 192x96, 6 = 192x192 one tile per workgroup, 7 = skinny M <= 64; 3/4/17/18 timing ablations; 19..31 tile order of the 192x192 kernel)", g_gemm_variant);
+    NTTile tile;   // per call (vtGemmNT.tile); the library holds no tile setting of its own
+    VT_CHECK_ARG(decode_nt_tile(p.tile, tile), "vt_gemm_nt: tile %d (0 auto, 1 = 128x128 2-deep ring, 16 = 128x128 4-deep ring, 2 = 192x192, 5 = 192x96, 6 = 192x192 one tile per workgroup, 7 = skinny M <= 64, 19..31 = tile order of the 192x192 kernel)", p.tile);
     VT_CHECK_ARG(p.M > 0 && p.N > 0 && p.K > 0 && p.K % BK == 0, "vt_gemm_nt: K=%d must be a positive multiple of 64 (M=%d N=%d)", p.K, p.M, p.N);
     VT_CHECK_ARG(p.lda % 8 == 0 && p.ldb % 8 == 0 && p.lda >= p.K && p.ldb >= p.K, "vt_gemm_nt: lda/ldb must be >= K and multiples of 8");
     VT_CHECK_ARG(((uintptr_t)p.A & 15) == 0 && ((uintptr_t)p.B & 15) == 0, "vt_gemm_nt: A/B must be 16-byte aligned");
@@ -577,21 +585,15 @@ extern "C" int vt_gemm_nt(const vtGemmNT* ph, vtStream stream) {
     // that leave its last round mostly empty (the discriminator's M = 8 x 1025, N = 384 / 1152: 86 or 258 tiles) finish
     // sooner on 128x128 tiles, two workgroups per CU.
     // M <= 64 (the AR prior's decode steps): the weight-streaming kernel, N / 16 workgroups
-    if (g_gemm_variant == 7 || (g_gemm_variant == 0 && p.M <= 64 && !p.colsum_partial && p.N >= 64)) {
+    if (tile.kernel == NTTile::SKINNY || (tile.kernel == NTTile::AUTO && p.M <= 64 && !p.colsum_partial && p.N >= 64)) {
         VT_CHECK_ARG(p.M <= 64 && !p.colsum_partial, "vt_gemm_nt: tile 7 (skinny) needs M <= 64 and no colsum_partial (M=%d)", p.M);
         hipStream_t s = (hipStream_t)stream;
-        switch (p.epi) {
-            case VT_EPI_BF16: launch_skinny<VT_EPI_BF16>(p, s); break;
-            case VT_EPI_BF16_GELU: launch_skinny<VT_EPI_BF16_GELU>(p, s); break;
-            case VT_EPI_F32: launch_skinny<VT_EPI_F32>(p, s); break;
-            case VT_EPI_BF16_DGELU: launch_skinny<VT_EPI_BF16_DGELU>(p, s); break;
-            default: vt_set_error("vt_gemm_nt: unknown epilogue %d", p.epi); return VT_ERR_INVALID;
-        }
+        TRY(dispatch_epi(p.epi, [&](auto epi) { launch_skinny<decltype(epi)::value>(p, s); return VT_OK; }));
         VT_CHECK_LAUNCH("vt_gemm_nt(skinny)");
         return VT_OK;
     }
-    bool big = (g_gemm_variant >= 2 && g_gemm_variant != 7 && g_gemm_variant != 16) || p.colsum_partial;
-    if (g_gemm_variant == 0 && !big && p.N >= 192 && p.M >= 192) {
+    bool big = tile.kernel == NTTile::T192 || tile.kernel == NTTile::T192X96 || p.colsum_partial;
+    if (tile.kernel == NTTile::AUTO && !big && p.N >= 192 && p.M >= 192) {
         // cost in units of one full round of 192x192 tiles (256 workgroups, one per CU).  A partly filled last round of
         // that kernel costs a whole round; the 128x128 kernel runs two workgroups per CU (512 per round, a round ~1.05 of
         // a 192-round on equal work), and its last round is cheap while it leaves one workgroup per CU
@@ -605,13 +607,8 @@ extern "C" int vt_gemm_nt(const vtGemmNT* ph, vtStream stream) {
         big = c192 <= c128;
     }
     if (big) {
-        int rc = vt_gemm192_init();
-        if (rc) return rc;
-        // 19..31: tile order of the 192x192 kernel for A/B timing (19 = row-major list, 19 + W = column blocks of W tile columns); same results
-        const int order = (g_gemm_variant >= 19 && g_gemm_variant <= 31) ? g_gemm_variant - 19 : -1;
-        const int dbg = order >= 0 ? 0 : (g_gemm_variant == 3 || g_gemm_variant == 4) ? g_gemm_variant - 2 : g_gemm_variant >= 17 ? g_gemm_variant - 1 : g_gemm_variant >= 8 ? g_gemm_variant : 0;
-        const int half = g_gemm_variant == 5;
-        vt_gemm_nt192_launch(p, (hipStream_t)stream, dbg, half, g_gemm_variant == 6, order);
+        TRY(vt_gemm192_init());
+        TRY(vt_gemm_nt192_launch(p, (hipStream_t)stream, tile.kernel == NTTile::T192X96, tile.one_tile, tile.order));
         VT_CHECK_LAUNCH("vt_gemm_nt(192)");
         return VT_OK;
     }
@@ -621,24 +618,19 @@ extern "C" int vt_gemm_nt(const vtGemmNT* ph, vtStream stream) {
     a.tiles_n = (p.N + BN - 1) / BN;
     a.split = 1; a.part = nullptr; a.ctr = nullptr;
     const int tiles = a.tiles_m * a.tiles_n;
-    a.col_block = 0;   // set below, once the number of workgroups per CU is known
     hipStream_t s = (hipStream_t)stream;
     // At most one workgroup per CU (one or two clips per GPU): the 4-deep ring hides the load latency that a co-resident
     // workgroup would otherwise cover (same MFMA order, bit-identical results; tile 16 forces it, tile 1 keeps the 2-deep ring)
-    static const int n_cu = [] {
-        int dev = 0, n = 256;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        return n;
-    }();
+    const int n_cu = vt_gemm_num_cus();
     // Split K (only with a caller-supplied workspace): a launch that would leave most of the chip idle -- the N = 768 GEMMs of a
     // one- or two-clip step are 72 or 144 tiles with K up to 3072 -- gives each tile to `split` workgroups, each over a
     // contiguous share of the K-tiles; the last one to arrive adds the fp32 partial sums in split order and runs the epilogue.
     // Deterministic (run-to-run bit-identical), but NOT the unsplit kernel's summation order: results differ from tile 1 / 16 in
     // the last fp32 bits.  Automatic rule from tools/gemm_small_m.py on MI355X.
     const int nt_all = p.K / BK;
-    if (p.splitk_ws && p.splitk != 1 && (g_gemm_variant == 0 || g_gemm_variant == 1 || g_gemm_variant == 16)) {
+    if (p.splitk_ws && p.splitk != 1) {   // (only AUTO and the two forced 128x128 rings get here)
         int want = p.splitk;
-        if (want == 0 && g_gemm_variant == 0 && tiles < n_cu && nt_all >= 24) {
+        if (want == 0 && tile.kernel == NTTile::AUTO && tiles < n_cu && nt_all >= 24) {
             // the hand-off costs ~6 us (write-through stores, the counter, one read past the L2): K >= 1536 pays for it, K = 768 does not;
             // three partials are read back in one go, more would queue behind each other
             want = tiles * 3 <= 2 * n_cu ? 3 : 2;
@@ -655,44 +647,30 @@ extern "C" int vt_gemm_nt(const vtGemmNT* ph, vtStream stream) {
         }
     }
     const dim3 grid(tiles * a.split), block(256);
-    const bool deep = g_gemm_variant == 16 || (g_gemm_variant == 0 && (int)grid.x <= n_cu && nt_all / a.split >= 4);
-    {   // tile order: the tiles one XCD has in flight form a rectangle (vt_common.h); VT_GEMM_TILE_ORDER forces a width for whole-step A/B timing
-        static const int order_env = [] { const char* e = getenv("VT_GEMM_TILE_ORDER"); return (e && *e) ? atoi(e) : -1; }();
-        const int per_xcd = (deep ? 1 : 2) * n_cu / 8, chunk = ((int)grid.x + 7) / 8;
-        a.col_block = order_env >= 0 ? (order_env < a.tiles_n ? order_env : 0) : vt_auto_col_block(a.tiles_n, per_xcd < chunk ? per_xcd : chunk);
-    }
+    const bool deep = tile.kernel == NTTile::T128_RING4 || (tile.kernel == NTTile::AUTO && (int)grid.x <= n_cu && nt_all / a.split >= 4);
+    a.col_block = vt_gemm_col_block(-1, a.tiles_n, (int)grid.x, deep ? 1 : 2);
     if (deep) {
         static bool attr_set = false;
         constexpr int LDS4 = 4 * 2 * TILE_B;
         if (!attr_set) {
-            hipError_t e = hipFuncSetAttribute((const void*)gemm_nt_kernel<VT_EPI_BF16, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS4);
-            if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gemm_nt_kernel<VT_EPI_BF16_GELU, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS4);
-            if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gemm_nt_kernel<VT_EPI_F32, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS4);
-            if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gemm_nt_kernel<VT_EPI_BF16_DGELU, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS4);
+            hipError_t e = hipSuccess;
+            for (int epi : {VT_EPI_BF16, VT_EPI_BF16_GELU, VT_EPI_F32, VT_EPI_BF16_DGELU})
+                dispatch_epi(epi, [&](auto k) {
+                    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gemm_nt_kernel<decltype(k)::value, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS4);
+                    return 0;
+                });
             if (e != hipSuccess) {
                 vt_set_error("vt_gemm_nt: hipFuncSetAttribute(%d bytes of LDS) failed: %s", LDS4, hipGetErrorString(e));
                 return VT_ERR_LAUNCH;
             }
             attr_set = true;
         }
-        switch (p.epi) {
-            case VT_EPI_BF16: hipLaunchKernelGGL((gemm_nt_kernel<VT_EPI_BF16, 4>), grid, block, LDS4, s, a); break;
-            case VT_EPI_BF16_GELU: hipLaunchKernelGGL((gemm_nt_kernel<VT_EPI_BF16_GELU, 4>), grid, block, LDS4, s, a); break;
-            case VT_EPI_F32: hipLaunchKernelGGL((gemm_nt_kernel<VT_EPI_F32, 4>), grid, block, LDS4, s, a); break;
-            case VT_EPI_BF16_DGELU: hipLaunchKernelGGL((gemm_nt_kernel<VT_EPI_BF16_DGELU, 4>), grid, block, LDS4, s, a); break;
-            default: vt_set_error("vt_gemm_nt: unknown epilogue %d", p.epi); return VT_ERR_INVALID;
-        }
+        TRY(dispatch_epi(p.epi, [&](auto epi) { hipLaunchKernelGGL((gemm_nt_kernel<decltype(epi)::value, 4>), grid, block, LDS4, s, a); return VT_OK; }));
         VT_CHECK_LAUNCH("vt_gemm_nt(128, 4-deep)");
         return VT_OK;
     }
     const size_t lds = 4 * TILE_B;
-    switch (p.epi) {
-        case VT_EPI_BF16: hipLaunchKernelGGL((gemm_nt_kernel<VT_EPI_BF16, 2>), grid, block, lds, s, a); break;
-        case VT_EPI_BF16_GELU: hipLaunchKernelGGL((gemm_nt_kernel<VT_EPI_BF16_GELU, 2>), grid, block, lds, s, a); break;
-        case VT_EPI_F32: hipLaunchKernelGGL((gemm_nt_kernel<VT_EPI_F32, 2>), grid, block, lds, s, a); break;
-        case VT_EPI_BF16_DGELU: hipLaunchKernelGGL((gemm_nt_kernel<VT_EPI_BF16_DGELU, 2>), grid, block, lds, s, a); break;
-        default: vt_set_error("vt_gemm_nt: unknown epilogue %d", p.epi); return VT_ERR_INVALID;
-    }
+    TRY(dispatch_epi(p.epi, [&](auto epi) { hipLaunchKernelGGL((gemm_nt_kernel<decltype(epi)::value, 2>), grid, block, lds, s, a); return VT_OK; }));
     VT_CHECK_LAUNCH("vt_gemm_nt");
     return VT_OK;
 }
@@ -719,8 +697,7 @@ extern "C" int vt_gemm_tn_grouped(const vtGemmTN* ph, int32_t n, vtStream stream
         if (g_gemm_variant == 0 && (p.p_lim < 192 || p.q_lim < 192)) big = false;
     }
     if (big) {
-        int rc = vt_gemm192_init();
-        if (rc) return rc;
+        TRY(vt_gemm192_init());
         vt_gemm_tn192_launch(ph, n, (hipStream_t)stream, g_gemm_variant == 7);
         VT_CHECK_LAUNCH("vt_gemm_tn_grouped(192)");
         return VT_OK;

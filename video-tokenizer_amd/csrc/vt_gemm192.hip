@@ -17,55 +17,7 @@
 #include "vt_common.h"
 #include "vt_gemm_epilogue.h"
 
-// -DVT_GEMM_STORE8 (A/B builds only, tools/ab_variant.sh): keep the 8-byte epilogue stores of rounds 1-3
-#ifdef VT_GEMM_STORE8
-constexpr bool kStore16 = false;
-#else
-constexpr bool kStore16 = true;
-#endif
-
-// Diagnostic build only (-DVT_GEMM_STAMPS, tools/gemm_stamps.sh): s_memtime stamps around the segments of one OUTPUT tile of the NT kernel,
-// summed per wave: 0 main loop | 1 barrier + next tile's K-tile 0 issued | 2 accumulators -> LDS image | 3 barrier | 4 read-back + global stores |
-// 5 barrier, K-tiles 1-2 issued, wait for K-tile 0, barrier | 6 fragments of K-tile 0 | 7 output tiles.  Read the shares, not the run time.
-#ifdef VT_GEMM_STAMPS
-__device__ unsigned long long g_nt_stamps[256][8][8];
-#define VT_GSTAMP_DECL unsigned long long gs_t = __builtin_amdgcn_s_memtime(), gs_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}
-#define VT_GSTAMP(i)                                                     \
-    {                                                                    \
-        __builtin_amdgcn_sched_barrier(0);                               \
-        const unsigned long long gs_n = __builtin_amdgcn_s_memtime();    \
-        gs_acc[i] += gs_n - gs_t;                                        \
-        gs_t = gs_n;                                                     \
-        __builtin_amdgcn_sched_barrier(0);                               \
-    }
-#define VT_GSTAMP_FLUSH                                                  \
-    if ((threadIdx.x & 63) == 0 && blockIdx.x < 256)                     \
-        for (int i_ = 0; i_ < 8; ++i_) g_nt_stamps[blockIdx.x][threadIdx.x >> 6][i_] = gs_acc[i_]
-#else
-#define VT_GSTAMP_DECL
-#define VT_GSTAMP(i)
-#define VT_GSTAMP_FLUSH
-#endif
-
-// -DVT_GEMM_RESIDUAL_IN_LOOP (A/B builds only): the fp32 epilogue of rounds 1-3, one residual load per trip of its store loop
-#ifdef VT_GEMM_RESIDUAL_IN_LOOP
-constexpr bool kResidualFirst = false;
-#else
-constexpr bool kResidualFirst = true;
-#endif
-
 namespace {
-
-// A/B diagnostic (tools/r05_store_kind_ab.sh): which bf16 outputs of the epilogues leave by ORDINARY instead of streaming (nt) stores.
-// bit 0 = the plain bf16 output (qkv forward, input gradients), bit 1 = the GELU epilogue's u, bit 2 = its g, bit 3 = the gelu' output.
-#ifndef VT_GEMM_PLAIN_STORES
-#define VT_GEMM_PLAIN_STORES 0
-#endif
-template <int BIT, typename T>
-__device__ __forceinline__ void st_out(T* p, const T& v) {
-    if constexpr ((VT_GEMM_PLAIN_STORES >> BIT) & 1) *p = v;
-    else st_stream_any(p, v);
-}
 
 constexpr int TM = 192, TN_ = 192, TK = 64;
 constexpr int OP_BYTES = TM * TK * 2;      // 24 KiB per operand tile (both layouts)
@@ -85,7 +37,6 @@ struct NT192Args {
     vtGemmNT p;
     int tiles_m, tiles_n;
     int col_block;  // tile order: 0 = row-major list, W > 0 = column blocks of W tile columns, row-major inside a block (launch_nt192)
-    int dbg;      // timing experiments only (vtGemmNT.tile 3/4/17/18): 1 = no LDS-DMA after the prologue, 2 = no MFMA/LDS reads, 16 = no bf16 output stores, 17 = output stores onto a cache-resident region
 };
 
 // Geometry of the two NT instantiations.  WN = waves along N (each wave owns 96 x 48 outputs):
@@ -135,6 +86,27 @@ struct GeluTab {
 };
 __device__ __forceinline__ unsigned bf16_bits(bf16_t x) { return (unsigned)__builtin_bit_cast(unsigned short, x); }
 __device__ __forceinline__ bf16_t bf16_from_bits(unsigned b) { return __builtin_bit_cast(bf16_t, (unsigned short)b); }
+template <int N>
+using bf16xN = __bf16 __attribute__((ext_vector_type(N)));
+// gelu of the N bf16 values a lane read back.  TABLE: from the table at `tab`, unless some lane of the wave holds a value outside its range --
+// then the whole wave takes the arithmetic (wave-uniform branch; the same bits either way).
+template <int N, bool TABLE>
+__device__ __forceinline__ bf16xN<N> gelu_lookup(const bf16xN<N>& h, const bf16_t* tab) {
+    bf16xN<N> gl;
+    if constexpr (TABLE) {
+        unsigned idx[N], any = 0;
+#pragma unroll
+        for (int e = 0; e < N; ++e) { idx[e] = GeluTab<VT_EPI_BF16_GELU>::index(bf16_bits(h[e])); any |= idx[e]; }
+        if (__builtin_amdgcn_ballot_w64((any & 0x8000u) != 0) == 0) {
+#pragma unroll
+            for (int e = 0; e < N; ++e) gl[e] = tab[idx[e]];
+            return gl;
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < N; ++e) gl[e] = f2bf(gelu_erf(bf2f(h[e])));
+    return gl;
+}
 
 // The P 16-B-per-lane DMA pieces of a K-tile (pieces 0..PA-1 = A rows, PA..P-1 = B rows).  A lane's byte offset inside
 // its operand's [tile rows][K] panel does not depend on the K-tile (row clamp and swizzle are per row), so it is computed
@@ -295,15 +267,8 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm_nt192_kernel(const NT192Args
             ((bf16_t*)tab)[e] = f2bf(gelu_erf(x));
         }
     }
-    if (a.dbg >= 8 && ((blockIdx.x >> 3) & 1))          // timing experiment (vtGemmNT.tile 8..15): every other CU of an XCD starts 1..8 us late
-        for (int i = 0; i < a.dbg - 7; ++i) __builtin_amdgcn_s_sleep(32);
     constexpr bool PERSIST = WN == 4;   // the 192x96 experiment stays one tile per workgroup
-    VT_GSTAMP_DECL;
     for (int it = blockIdx.x; it < nwg; it = PERSIST ? it + (int)gridDim.x : nwg) {
-#ifdef VT_GEMM_STAMPS
-    gs_acc[7] += 1;
-    if (it == (int)blockIdx.x) gs_t = __builtin_amdgcn_s_memtime();
-#endif
     // K-tile 0 of this output tile is already in flight (issued above, or before the previous tile's epilogue)
     // (zeroed by instructions with an inline constant: as plain C++ the compiler keeps a zero register PAIR alive across the whole
     // persistent loop to copy from, and spills it in the instantiations that sit at the register limit)
@@ -325,7 +290,6 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm_nt192_kernel(const NT192Args
     else if (nt > 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(G::P) : "memory");
     else wait_vmcnt0();
     raw_barrier();
-    VT_GSTAMP(5);
     bf16x8 xa0[6], xb0[3], xa1[6], xb1[3], ya0[6], yb0[3], ya1[6], yb1[3];
     {   // fragments of tile 0
         const unsigned s0 = sbase + slot_of(0) * G::STAGE;
@@ -340,7 +304,6 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm_nt192_kernel(const NT192Args
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
     }
-    VT_GSTAMP(6);
     for (int t = 0;;) {
         // tile t from set X, prefetch tile t+1 into set Y.  The prefetch is unconditional (branch-free tile body, one
         // body per register set): after the last tile it re-reads a valid, quiescent LDS buffer into the unused set.
@@ -348,18 +311,18 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm_nt192_kernel(const NT192Args
             const bool more = t + 1 < nt;
             if (more) sync_for(t + 1);
             const unsigned nb = sbase + slot_of(more ? t + 1 : t) * G::STAGE;
-            const int dma_tile = (t + G::NST < nt && a.dbg != 1) ? t + G::NST : -1;  // goes into the buffer tile t just vacated
+            const int dma_tile = t + G::NST < nt ? t + G::NST : -1;  // goes into the buffer tile t just vacated
             const unsigned dma_dst = sbase + slot_of(t) * G::STAGE;
-            if (a.dbg != 2) VT_STEP(xa0, xb0, xa1, xb1, ya0, yb0, ya1, yb1, nb, true)
+            VT_STEP(xa0, xb0, xa1, xb1, ya0, yb0, ya1, yb1, nb, true)
             if (++t == nt) break;
         }
         {   // tile t from set Y, prefetch tile t+1 into set X
             const bool more = t + 1 < nt;
             if (more) sync_for(t + 1);
             const unsigned nb = sbase + slot_of(more ? t + 1 : t) * G::STAGE;
-            const int dma_tile = (t + G::NST < nt && a.dbg != 1) ? t + G::NST : -1;
+            const int dma_tile = t + G::NST < nt ? t + G::NST : -1;
             const unsigned dma_dst = sbase + slot_of(t) * G::STAGE;
-            if (a.dbg != 2) VT_STEP(ya0, yb0, ya1, yb1, xa0, xb0, xa1, xb1, nb, true)
+            VT_STEP(ya0, yb0, ya1, yb1, xa0, xb0, xa1, xb1, nb, true)
             if (++t == nt) break;
         }
     }
@@ -371,15 +334,13 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm_nt192_kernel(const NT192Args
     // every wave is done with the ring: start the next output tile's K-tile 0 into slot 2 (the epilogue below only uses
     // slots 0-1), then write this tile out
     const int em0 = m0, en0 = n0;
-    VT_GSTAMP(0);
     raw_barrier();
     if constexpr (PERSIST) {
         if (it + (int)gridDim.x < nwg) {
             set_tile(it + gridDim.x);
-            if (a.dbg != 1) issue_tile(0);
+            issue_tile(0);
         }
     }
-    VT_GSTAMP(1);
 
     if constexpr (EPI != VT_EPI_F32) {
         if ((p.N & 3) == 0) {
@@ -425,9 +386,7 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm_nt192_kernel(const NT192Args
                     const f32x4 v = acc[i][j] + b4[j];
                     *(bf16x4*)(smem + (wm * 96 + i * 16 + fr_e) * STRIDE + (wn * 12 + j * 4 + fq_e) * 8) = (bf16x4){f2bf(v[0]), f2bf(v[1]), f2bf(v[2]), f2bf(v[3])};
                 }
-            VT_GSTAMP(2);
             __syncthreads();
-            VT_GSTAMP(3);
             if constexpr (EPI == VT_EPI_BF16_DGELU) {
                 // a thread keeps ONE 4-column group and walks the rows (48 lanes cover a 384-B row, the rest of the wave the
                 // next row), so the column sums of the rounded output -- the bias gradient of the Linear whose
@@ -445,7 +404,7 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm_nt192_kernel(const NT192Args
                             const bf16x4 uu = uu_pre[it];
                             const bf16x4 r = {f2bf(bf2f(h[0]) * gelu_erf_grad(bf2f(uu[0]))), f2bf(bf2f(h[1]) * gelu_erf_grad(bf2f(uu[1]))),
                                               f2bf(bf2f(h[2]) * gelu_erf_grad(bf2f(uu[2]))), f2bf(bf2f(h[3]) * gelu_erf_grad(bf2f(uu[3])))};
-                            st_out<3>((bf16x4*)((bf16_t*)p.out + (int64_t)m * p.ldo + n), r);
+                            st_stream_any((bf16x4*)((bf16_t*)p.out + (int64_t)m * p.ldo + n), r);
                             cs += (f32x4){bf2f(r[0]), bf2f(r[1]), bf2f(r[2]), bf2f(r[3])};
                         }
                     }
@@ -466,7 +425,7 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm_nt192_kernel(const NT192Args
             // Round 4: 16 bytes per lane on the way out (two 8-byte image reads, ONE global_store_dwordx4: a wave instruction writes 1 KiB).
             // 8-byte accesses run at 0.54-0.70 of the 16-byte rate (MI355X_MICROARCH, visibility table) and the epilogue is what a round
             // of this kernel pays outside its main loop (6-13 us, all 256 CUs storing at once).  Needs 8-column alignment of the output.
-            if (kStore16 && a.dbg == 0 && (p.N & 7) == 0 && (p.ldo & 7) == 0 && (EPI != VT_EPI_BF16_GELU || (p.ldo2 & 7) == 0)) {
+            if ((p.N & 7) == 0 && (p.ldo & 7) == 0 && (EPI != VT_EPI_BF16_GELU || (p.ldo2 & 7) == 0)) {
                 constexpr int UPR16 = G::TNW / 8;                        // 16-B units per tile row
                 constexpr int NIT16 = TM * UPR16 / G::THREADS, RB16 = 3;
                 static_assert(NIT16 % RB16 == 0, "read-back batches");
@@ -488,36 +447,16 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm_nt192_kernel(const NT192Args
                         const int m = em0 + piece_row(it0 + u), n = en0 + piece_col(it0 + u);
                         if (m >= p.M || n >= p.N) continue;
                         const bf16x8 h = hh[u];
-                        st_out<(EPI == VT_EPI_BF16_GELU ? 1 : 0)>((bf16x8*)((bf16_t*)p.out + (int64_t)m * p.ldo + n), h);
+                        st_stream_any((bf16x8*)((bf16_t*)p.out + (int64_t)m * p.ldo + n), h);
                         if constexpr (EPI == VT_EPI_BF16_GELU) {
-                            bf16x8 gl;
-                            bool looked_up = false;
-                            if constexpr (TABLE) {
-                                unsigned idx[8], any = 0;
-#pragma unroll
-                                for (int e = 0; e < 8; ++e) { idx[e] = GT::index(bf16_bits(h[e])); any |= idx[e]; }
-                                if (__builtin_amdgcn_ballot_w64((any & 0x8000u) != 0) == 0) {
-#pragma unroll
-                                    for (int e = 0; e < 8; ++e) gl[e] = ((const bf16_t*)tab)[idx[e]];
-                                    looked_up = true;
-                                }
-                            }
-                            if (!looked_up) {
-#pragma unroll
-                                for (int e = 0; e < 8; ++e) gl[e] = f2bf(gelu_erf(bf2f(h[e])));
-                            }
-                            st_out<2>((bf16x8*)((bf16_t*)p.out2 + (int64_t)m * p.ldo2 + n), gl);
+                            st_stream_any((bf16x8*)((bf16_t*)p.out2 + (int64_t)m * p.ldo2 + n), gelu_lookup<8, TABLE>(h, (const bf16_t*)tab));
                         }
                     }
                 }
-                VT_GSTAMP(4);
-                if (it + (int)gridDim.x >= nwg) { VT_GSTAMP_FLUSH; }
                 continue;
             }
             // read-back in batches of RB image reads followed by their stores: with one read in flight per store (the compiler's order for
             // the plain loop) every store waits a full LDS round trip
-            // timing ablation (tile 18): every store of this workgroup lands on ONE tile-sized, cache-resident region (wave-uniform shift)
-            const int64_t dbg_shift = a.dbg == 17 ? ((int64_t)((int)(blockIdx.x & 63) * TM - em0) * p.ldo - en0) : 0;
             constexpr int NITS = TM * UPR / G::THREADS, RB = 3;
             static_assert(NITS % RB == 0, "read-back batches");
 #pragma unroll 1
@@ -536,21 +475,10 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm_nt192_kernel(const NT192Args
                     const int m = em0 + row, n = en0 + c * 4;
                     if (m >= p.M || n >= p.N) continue;
                     const bf16x4 h = hh[u];
-                    if (a.dbg == 16 && bf16_bits(h[0]) != 0x7FC1u) continue;          // timing ablation (tile 17): no output stores
-                    bf16_t* o = (bf16_t*)p.out + dbg_shift + (int64_t)m * p.ldo + n;
-                    st_out<(EPI == VT_EPI_BF16_GELU ? 1 : 0)>((bf16x4*)o, h);
+                    bf16_t* o = (bf16_t*)p.out + (int64_t)m * p.ldo + n;
+                    st_stream_any((bf16x4*)o, h);
                     if constexpr (EPI == VT_EPI_BF16_GELU) {
-                        bf16x4 gl;
-                        bool looked_up = false;
-                        if constexpr (TABLE) {
-                            const unsigned i0 = GT::index(bf16_bits(h[0])), i1 = GT::index(bf16_bits(h[1])), i2 = GT::index(bf16_bits(h[2])), i3 = GT::index(bf16_bits(h[3]));
-                            if (__builtin_amdgcn_ballot_w64(((i0 | i1 | i2 | i3) & 0x8000u) != 0) == 0) {
-                                gl = (bf16x4){((const bf16_t*)tab)[i0], ((const bf16_t*)tab)[i1], ((const bf16_t*)tab)[i2], ((const bf16_t*)tab)[i3]};
-                                looked_up = true;
-                            }
-                        }
-                        if (!looked_up) gl = (bf16x4){f2bf(gelu_erf(bf2f(h[0]))), f2bf(gelu_erf(bf2f(h[1]))), f2bf(gelu_erf(bf2f(h[2]))), f2bf(gelu_erf(bf2f(h[3])))};
-                        st_out<2>((bf16x4*)((bf16_t*)p.out2 + dbg_shift + (int64_t)m * p.ldo2 + n), gl);
+                        st_stream_any((bf16x4*)((bf16_t*)p.out2 + (int64_t)m * p.ldo2 + n), gelu_lookup<4, TABLE>(h, (const bf16_t*)tab));
                     }
                 }
             }
@@ -584,7 +512,7 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm_nt192_kernel(const NT192Args
                 constexpr int NU = 96 * 48 / G::THREADS;
                 // output row of tile row d without a division per piece: the tile starts at group q0, row r0 of the row map, and with
                 // grp >= 192 it crosses at most one group boundary (other maps take the rolled loop below)
-                const bool cheap_map = kResidualFirst && (omap.grp == 0 || omap.grp >= TM);
+                const bool cheap_map = omap.grp == 0 || omap.grp >= TM;
                 const int q0 = omap.grp ? em0 / omap.grp : 0, r0 = omap.grp ? em0 - q0 * omap.grp : em0;
                 auto orow_of = [&](int d) -> int64_t {
                     const int r = r0 + d;
@@ -723,6 +651,22 @@ __device__ __forceinline__ bf16x8 frag_tn192(const char* lds, int col, int kb, i
     return cat4(lo, hi);
 }
 
+// The problem that entry `sid` of the launch's tile list belongs to, and the first row / column (p0, q0) of its tile there.
+// Tiles walk in groups of 4 p-rows, p fastest: an XCD's round of 32 consecutive tiles is a 4 x 8 (or 8 x 4) block of the output,
+// i.e. 12 operand panels instead of the 18 a row-major walk gives a wide problem (fc2's 4 x 16 tiles: 2 x 16 per round)
+__device__ __forceinline__ const vtGemmTN& tn192_locate(const TN192Args& a, int sid, int& p0, int& q0) {
+    int g = 0;
+    while (g + 1 < a.n && sid >= a.tile_start[g + 1]) ++g;
+    const vtGemmTN& p = a.p[g];
+    const int local = sid - a.tile_start[g];
+    const int tiles_q = (p.q_lim + TN_ - 1) / TN_;
+    const int tiles_p = (p.p_lim + TM - 1) / TM;
+    const int grp4 = local / (4 * tiles_q), rem4 = local - grp4 * 4 * tiles_q;
+    const int rows4 = min(4, tiles_p - grp4 * 4);
+    p0 = (grp4 * 4 + rem4 % rows4) * TM, q0 = (rem4 / rows4) * TN_;
+    return p;
+}
+
 __global__ __launch_bounds__(512, 2) void gemm_tn192_kernel(const TN192Args a) {
     extern __shared__ __attribute__((aligned(128))) char smem[];
     const int tid = threadIdx.x;
@@ -730,19 +674,8 @@ __global__ __launch_bounds__(512, 2) void gemm_tn192_kernel(const TN192Args a) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 2, wn = wave & 3;
 
-    const int nwg = a.tile_start[a.n];
-    const int sid = xcd_remap(blockIdx.x, nwg);
-    int g = 0;
-    while (g + 1 < a.n && sid >= a.tile_start[g + 1]) ++g;
-    const vtGemmTN& p = a.p[g];
-    const int local = sid - a.tile_start[g];
-    const int tiles_q = (p.q_lim + TN_ - 1) / TN_;
-    // tiles walk in groups of 4 p-rows, p fastest: an XCD's round of 32 consecutive tiles is a 4 x 8 (or 8 x 4) block of the output,
-    // i.e. 12 operand panels instead of the 18 a row-major walk gives a wide problem (fc2's 4 x 16 tiles: 2 x 16 per round)
-    const int tiles_p = (p.p_lim + TM - 1) / TM;
-    const int grp4 = local / (4 * tiles_q), rem4 = local - grp4 * 4 * tiles_q;
-    const int rows4 = min(4, tiles_p - grp4 * 4);
-    const int p0 = (grp4 * 4 + rem4 % rows4) * TM, q0 = (rem4 / rows4) * TN_;
+    int p0, q0;
+    const vtGemmTN& p = tn192_locate(a, xcd_remap(blockIdx.x, a.tile_start[a.n]), p0, q0);
     const bf16_t* A = (const bf16_t*)p.A;
     const bf16_t* B = (const bf16_t*)p.B;
 
@@ -811,24 +744,7 @@ __global__ __launch_bounds__(512, 2) void gemm_tn192_kernel(const TN192Args a) {
         cur = cur + 1 == NSTAGE ? 0 : cur + 1;
     }
 
-    const int fr = lane & 15, fq = lane >> 4;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        const int pr = p0 + wm * 96 + i * 16 + fr;
-        if (pr >= p.p_lim) continue;
-        const int64_t orow = p.row_perm ? (int64_t)p.row_perm[pr] : (int64_t)pr;
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const int qc = q0 + wn * 48 + j * 16 + fq * 4;
-            if (qc >= p.q_lim) continue;
-            float* o = p.out + orow * p.ldo + qc;
-            if (qc + 3 < p.q_lim && ((p.ldo & 3) == 0)) {
-                *(f32x4*)o = acc[i][j];
-            } else {
-                for (int r = 0; r < 4 && qc + r < p.q_lim; ++r) o[r] = acc[i][j][r];
-            }
-        }
-    }
+    tn_store_acc(p, acc, p0 + wm * 96, q0 + wn * 48, lane);
 }
 
 
@@ -849,19 +765,8 @@ __global__ __launch_bounds__(512, 2) void gemm_tn192p_kernel(const TN192Args a) 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 2, wn = wave & 3;
 
-    const int nwg = a.tile_start[a.n];
-    const int sid = xcd_remap(blockIdx.x, nwg);
-    int g = 0;
-    while (g + 1 < a.n && sid >= a.tile_start[g + 1]) ++g;
-    const vtGemmTN& p = a.p[g];
-    const int local = sid - a.tile_start[g];
-    const int tiles_q = (p.q_lim + TN_ - 1) / TN_;
-    // tiles walk in groups of 4 p-rows, p fastest: an XCD's round of 32 consecutive tiles is a 4 x 8 (or 8 x 4) block of the output,
-    // i.e. 12 operand panels instead of the 18 a row-major walk gives a wide problem (fc2's 4 x 16 tiles: 2 x 16 per round)
-    const int tiles_p = (p.p_lim + TM - 1) / TM;
-    const int grp4 = local / (4 * tiles_q), rem4 = local - grp4 * 4 * tiles_q;
-    const int rows4 = min(4, tiles_p - grp4 * 4);
-    const int p0 = (grp4 * 4 + rem4 % rows4) * TM, q0 = (rem4 / rows4) * TN_;
+    int p0, q0;
+    const vtGemmTN& p = tn192_locate(a, xcd_remap(blockIdx.x, a.tile_start[a.n]), p0, q0);
     const bf16_t* A = (const bf16_t*)p.A;
     const bf16_t* B = (const bf16_t*)p.B;
 
@@ -1005,30 +910,10 @@ __global__ __launch_bounds__(512, 2) void gemm_tn192p_kernel(const TN192Args a) 
 #undef VT_MROW
 #undef VT_TSTEP
 
-    const int fr = lane & 15, fq = lane >> 4;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        const int pr = p0 + wm * 96 + i * 16 + fr;
-        if (pr >= p.p_lim) continue;
-        const int64_t orow = p.row_perm ? (int64_t)p.row_perm[pr] : (int64_t)pr;
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const int qc = q0 + wn * 48 + j * 16 + fq * 4;
-            if (qc >= p.q_lim) continue;
-            float* o = p.out + orow * p.ldo + qc;
-            if (qc + 3 < p.q_lim && ((p.ldo & 3) == 0)) {
-                *(f32x4*)o = acc[i][j];
-            } else {
-                for (int r = 0; r < 4 && qc + r < p.q_lim; ++r) o[r] = acc[i][j][r];
-            }
-        }
-    }
+    tn_store_acc(p, acc, p0 + wm * 96, q0 + wn * 48, lane);
 }
 
 }  // namespace
-
-static int g_num_cus = 256;   // set by vt_gemm192_init from the device properties
-static int g_order_env = -1;   // VT_GEMM_TILE_ORDER (read once by vt_gemm192_init): A/B timing of the tile order inside a whole step; -1 = automatic
 
 // Tile order of a launch.  The tile list is dealt to the 8 XCDs in contiguous chunks (xcd_remap); with a row-major list the ~32 tiles in
 // flight on one XCD are 32 / tiles_n whole tile rows, i.e. 32 / tiles_n A panels + ALL tiles_n B panels stream through its 4-MB L2 per round
@@ -1039,44 +924,54 @@ static int g_order_env = -1;   // VT_GEMM_TILE_ORDER (read once by vt_gemm192_in
 // The width is vt_auto_col_block(tile columns, 32 tiles in flight per XCD): 6 for qkv forward (12 columns) and for N = 3072 (16 columns: 6 + 6 + 4;
 // 6 and 8 measure the same there), row-major for the 4 tile columns of N = 768.
 
-template <int WN>
-static int nt192_in_flight(int ntiles) {   // tiles one XCD works on at a time
-    const int per_xcd = (WN == 4 ? 1 : 2) * g_num_cus / 8, chunk = (ntiles + 7) / 8;
-    return per_xcd < chunk ? per_xcd : chunk;
+int vt_gemm_num_cus() {   // of the current device, queried once
+    static const int n_cu = [] {
+        int dev = 0, n = 256;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+        return n;
+    }();
+    return n_cu;
 }
+
+// col_block of an NT launch of `nwg` workgroups, `wg_per_cu` of them resident per CU.  forced >= 0: that order (vtGemmNT.tile = 19 + forced); else
+// VT_GEMM_TILE_ORDER of the environment (read once: A/B timing of the order inside a whole step); else automatic.  A forced width that does not
+// fit the tile columns falls back to the row-major list.
+int vt_gemm_col_block(int forced, int tiles_n, int nwg, int wg_per_cu) {
+    static const int order_env = [] { const char* e = getenv("VT_GEMM_TILE_ORDER"); return (e && *e) ? atoi(e) : -1; }();
+    const int order = forced >= 0 ? forced : order_env;
+    if (order >= 0) return order < tiles_n ? order : 0;
+    const int per_xcd = wg_per_cu * vt_gemm_num_cus() / 8, chunk = (nwg + 7) / 8;   // tiles one XCD works on at a time
+    return vt_auto_col_block(tiles_n, per_xcd < chunk ? per_xcd : chunk);
+}
+
+// dynamic LDS of gemm_nt192_kernel<EPI, WN>: the ring, and the GELU table behind it
+template <int EPI, int WN>
+static constexpr int nt192_lds_bytes() { return NTGeo<WN>::NST * NTGeo<WN>::STAGE + (WN == 4 ? GeluTab<EPI>::BYTES : 0); }
 
 // Called by vt_gemm_nt / vt_gemm_tn_grouped (vt_gemm.hip) after argument validation.
 template <int WN>
-static void launch_nt192(const vtGemmNT& p, hipStream_t s, int dbg, int one_tile, int order) {
+static int launch_nt192(const vtGemmNT& p, hipStream_t s, int one_tile, int order) {
     using G = NTGeo<WN>;
     NT192Args a;
     a.p = p;
-    a.dbg = dbg;
     a.tiles_m = (p.M + TM - 1) / TM;
     a.tiles_n = (p.N + G::TNW - 1) / G::TNW;
-    if (order < 0) order = g_order_env;
-    a.col_block = order >= 0 ? (order < a.tiles_n ? order : 0) : vt_auto_col_block(a.tiles_n, nt192_in_flight<WN>(a.tiles_m * a.tiles_n));
+    const int ntiles = a.tiles_m * a.tiles_n;
+    a.col_block = vt_gemm_col_block(order, a.tiles_n, ntiles, WN == 4 ? 1 : 2);
     // WN == 4: persistent, one workgroup per CU walks tiles b, b + grid, ...; one_tile (vtGemmNT.tile = 6, the data-parallel backward): one
     // tile per workgroup, so that the hardware dispatcher hands tiles to whichever CU is free while a collective's workgroups hold some.
-    // A launch mode, not a timing ablation: `dbg` stays 0 and every epilogue keeps its production store path
-    const int ntiles = a.tiles_m * a.tiles_n;
-    const int persist = (WN == 4 && !one_tile) ? g_num_cus : ntiles;
+    const int persist = (WN == 4 && !one_tile) ? vt_gemm_num_cus() : ntiles;
     const dim3 grid(ntiles < persist ? ntiles : persist), block(G::THREADS);
-    const size_t lds = G::NST * G::STAGE;
-    constexpr size_t tab_gelu = WN == 4 ? GeluTab<VT_EPI_BF16_GELU>::BYTES : 0;
-    switch (p.epi) {
-        case VT_EPI_BF16: hipLaunchKernelGGL((gemm_nt192_kernel<VT_EPI_BF16, WN>), grid, block, lds, s, a); break;
-        case VT_EPI_BF16_GELU: hipLaunchKernelGGL((gemm_nt192_kernel<VT_EPI_BF16_GELU, WN>), grid, block, lds + tab_gelu, s, a); break;
-        case VT_EPI_F32: hipLaunchKernelGGL((gemm_nt192_kernel<VT_EPI_F32, WN>), grid, block, lds, s, a); break;
-        default: hipLaunchKernelGGL((gemm_nt192_kernel<VT_EPI_BF16_DGELU, WN>), grid, block, lds, s, a); break;
-    }
+    return dispatch_epi(p.epi, [&](auto epi) {
+        constexpr int EPI = decltype(epi)::value, LDS = nt192_lds_bytes<EPI, WN>();
+        hipLaunchKernelGGL((gemm_nt192_kernel<EPI, WN>), grid, block, LDS, s, a);
+        return VT_OK;
+    });
 }
 
 // half == 0: 192x192 tiles, one workgroup per CU; half != 0: 192x96 tiles, two per CU
-int vt_gemm_nt192_launch(const vtGemmNT& p, hipStream_t s, int dbg, int half, int one_tile, int order) {
-    if (half) launch_nt192<2>(p, s, dbg, one_tile, order);
-    else launch_nt192<4>(p, s, dbg, one_tile, order);
-    return 0;
+int vt_gemm_nt192_launch(const vtGemmNT& p, hipStream_t s, int half, int one_tile, int order) {
+    return half ? launch_nt192<2>(p, s, one_tile, order) : launch_nt192<4>(p, s, one_tile, order);
 }
 
 int vt_gemm_tn192_launch(const vtGemmTN* ph, int n, hipStream_t s, int burst) {
@@ -1094,40 +989,23 @@ int vt_gemm_tn192_launch(const vtGemmTN* ph, int n, hipStream_t s, int burst) {
     return 0;
 }
 
-template <int EPI, int WN>
-static hipError_t allow_lds_nt() {
-    return hipFuncSetAttribute((const void*)gemm_nt192_kernel<EPI, WN>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               NTGeo<WN>::NST * NTGeo<WN>::STAGE + (WN == 4 ? GeluTab<EPI>::BYTES : 0));
-}
-
-#ifdef VT_GEMM_STAMPS
-extern "C" int vt_gemm_nt_stamps(unsigned long long* host_out) {   // diagnostic build only: 256 x 8 x 8 counters
-    return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_nt_stamps), sizeof(g_nt_stamps)) == hipSuccess ? VT_OK : VT_ERR_LAUNCH;
-}
-#endif
-
 int vt_gemm192_init() {
     // more dynamic LDS than the 64 KiB default: opt in once per kernel
     static bool done = false;
     if (done) return 0;
     hipError_t e = hipSuccess;
-    if (e == hipSuccess) e = allow_lds_nt<VT_EPI_BF16, 4>();
-    if (e == hipSuccess) e = allow_lds_nt<VT_EPI_BF16_GELU, 4>();
-    if (e == hipSuccess) e = allow_lds_nt<VT_EPI_F32, 4>();
-    if (e == hipSuccess) e = allow_lds_nt<VT_EPI_BF16_DGELU, 4>();
-    if (e == hipSuccess) e = allow_lds_nt<VT_EPI_BF16, 2>();
-    if (e == hipSuccess) e = allow_lds_nt<VT_EPI_BF16_GELU, 2>();
-    if (e == hipSuccess) e = allow_lds_nt<VT_EPI_F32, 2>();
-    if (e == hipSuccess) e = allow_lds_nt<VT_EPI_BF16_DGELU, 2>();
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gemm_tn192_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, NSTAGE * STAGE_BYTES);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gemm_tn192p_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, NSTAGE * STAGE_BYTES);
-    if (e == hipSuccess) {
-        int dev = 0, cus = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0)
-            g_num_cus = cus;
-        const char* ord = getenv("VT_GEMM_TILE_ORDER");
-        if (ord && *ord) g_order_env = atoi(ord);
-    }
+    auto allow = [&](const void* kernel, int bytes) {
+        if (e == hipSuccess) e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    };
+    for (int epi : {VT_EPI_BF16, VT_EPI_BF16_GELU, VT_EPI_F32, VT_EPI_BF16_DGELU})
+        dispatch_epi(epi, [&](auto k) {
+            constexpr int EPI = decltype(k)::value;
+            allow((const void*)gemm_nt192_kernel<EPI, 4>, nt192_lds_bytes<EPI, 4>());
+            allow((const void*)gemm_nt192_kernel<EPI, 2>, nt192_lds_bytes<EPI, 2>());
+            return 0;
+        });
+    allow((const void*)gemm_tn192_kernel, NSTAGE * STAGE_BYTES);
+    allow((const void*)gemm_tn192p_kernel, NSTAGE * STAGE_BYTES);
     if (e != hipSuccess) {
         vt_set_error("vt_gemm192_init: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
         return VT_ERR_LAUNCH;

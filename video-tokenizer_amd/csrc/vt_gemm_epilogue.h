@@ -3,7 +3,21 @@
 // Interior tiles (n + 3 < N) take the vector path: 16-B loads of bias / residual / rowmod / aux, one 8- or
 // 16-B store per output.  Only the last, ragged column group of a matrix takes the scalar path.
 #pragma once
+#include <type_traits>
+
 #include "vt_common.h"
+
+// Calls f with the run-time epilogue `epi` as a compile-time constant (std::integral_constant<int, VT_EPI_*>) and returns what it returns.
+template <typename F>
+static inline int dispatch_epi(int epi, F&& f) {
+    switch (epi) {
+        case VT_EPI_BF16: return f(std::integral_constant<int, VT_EPI_BF16>{});
+        case VT_EPI_BF16_GELU: return f(std::integral_constant<int, VT_EPI_BF16_GELU>{});
+        case VT_EPI_F32: return f(std::integral_constant<int, VT_EPI_F32>{});
+        case VT_EPI_BF16_DGELU: return f(std::integral_constant<int, VT_EPI_BF16_DGELU>{});
+        default: vt_set_error("vt_gemm_nt: unknown epilogue %d", epi); return VT_ERR_INVALID;
+    }
+}
 
 template <int EPI>
 __device__ __forceinline__ void nt_epilogue(const vtGemmNT& p, const RowMap& omap, int m, int n, const f32x4& acc4) {
@@ -53,6 +67,32 @@ __device__ __forceinline__ void nt_epilogue(const vtGemmNT& p, const RowMap& oma
             if (p.out_scale != 0.f) v *= p.out_scale;
             ((float*)p.out)[orow * p.ldo + n + r] = v;
             if (p.out2) ((bf16_t*)p.out2)[orow * p.ldo2 + n + r] = f2bf(v);
+        }
+    }
+}
+
+// Output of the TN kernels: a wave's NI x NJ accumulators start at (row0, col0) of C; after the swapped MFMA acc[i][j][r] =
+// C[row0 + i*16 + (lane&15)][col0 + j*16 + (lane>>4)*4 + r].  Rows >= p_lim and columns >= q_lim are not stored; row_perm scatters the rows.
+// `p` is taken BY VALUE: its fields are read once, into registers.  Through a reference into the kernel arguments they are re-read after
+// every store that might alias them, and gemm_tn_kernel then stops hoisting its staging addresses out of the K loop (5 % slower, measured).
+template <int NI, int NJ>
+__device__ __forceinline__ void tn_store_acc(const vtGemmTN p, const f32x4 (&acc)[NI][NJ], int row0, int col0, int lane) {
+    const int fr = lane & 15, fq = lane >> 4;
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+        const int pr = row0 + i * 16 + fr;
+        if (pr >= p.p_lim) continue;
+        const int64_t orow = p.row_perm ? (int64_t)p.row_perm[pr] : (int64_t)pr;
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const int qc = col0 + j * 16 + fq * 4;
+            if (qc >= p.q_lim) continue;
+            float* o = p.out + orow * p.ldo + qc;
+            if (qc + 3 < p.q_lim && ((p.ldo & 3) == 0)) {
+                *(f32x4*)o = acc[i][j];
+            } else {
+                for (int r = 0; r < 4 && qc + r < p.q_lim; ++r) o[r] = acc[i][j][r];
+            }
         }
     }
 }
