@@ -525,7 +525,10 @@ def test_attention_fwd_bwd(hip, B, L, H, hd):
     assert err < 3e-2, err
 
 
-@pytest.mark.parametrize("B,L,H,hd,q_begin", [(2, 192, 2, 64, 64), (1, 320, 3, 64, 128), (2, 200, 2, 32, 64), (1, 1536, 1, 64, 1024)])
+# the last three rows: no ragged tile and an odd first query tile in the dK/dV sweep (one tile; three tiles, whose second trip runs
+# its first half only; the last tile only, head_dim 32) -- buffer parity and the "stage t + 2" guard of the shared tile loop
+@pytest.mark.parametrize("B,L,H,hd,q_begin", [(2, 192, 2, 64, 64), (1, 320, 3, 64, 128), (2, 200, 2, 32, 64), (1, 1536, 1, 64, 1024),
+                                              (2, 128, 2, 64, 64), (2, 256, 2, 64, 64), (1, 256, 2, 32, 192)])
 def test_attention_kept_query_suffix(hip, B, L, H, hd, q_begin):
     """vt_attention_*_rows: queries q_begin..L-1 only (last block of a stack), compact o / dO, full-length keys and dqkv"""
     qkv = bf(_rand((B * L, 3 * H * hd), 150 + L))

@@ -29,33 +29,83 @@
 
 #include "vt_attn_tile.h"
 
-// Diagnostic build only (-DVT_ATTN_STAMPS, tools/attn_stamps.sh): s_memtime stamps around the three segments of a tile iteration
-// (tile body = staging issue + MFMA / softmax | s_waitcnt vmcnt(0) on the next tile's LDS-DMA | workgroup barrier), summed per wave.
-// The shares are what to read, never the run time (cdna_hip_programming.md section 7, "In-kernel stamps").
-#ifdef VT_ATTN_STAMPS
-__device__ unsigned long long g_attn_stamps[3][2048][4][6];     // [kernel: fwd, dq, dkv][workgroup][wave][body, drain, barrier, iterations, realtime at loop start, at loop end (100 MHz)]
-#define VT_STAMP_DECL unsigned long long st_t = __builtin_amdgcn_s_memtime(), st_acc[6] = {0, 0, 0, 0, __builtin_amdgcn_s_memrealtime(), 0}
-#define VT_STAMP(i)                                                      \
-    {                                                                    \
-        const unsigned long long st_n = __builtin_amdgcn_s_memtime();    \
-        st_acc[i] += st_n - st_t;                                        \
-        st_t = st_n;                                                     \
-    }
-#define VT_STAMP_ITER st_acc[3] += 1
-#define VT_STAMP_START st_t = __builtin_amdgcn_s_memtime()
-#define VT_STAMP_FLUSH(kern)                                                                                       \
-    st_acc[5] = __builtin_amdgcn_s_memrealtime();                                                                  \
-    if ((threadIdx.x & 63) == 0 && blockIdx.x < 2048)                                                              \
-        for (int i_ = 0; i_ < 6; ++i_) g_attn_stamps[kern][blockIdx.x][threadIdx.x >> 6][i_] = st_acc[i_]
-#else
-#define VT_STAMP_DECL
-#define VT_STAMP(i)
-#define VT_STAMP_ITER
-#define VT_STAMP_START
-#define VT_STAMP_FLUSH(kern)
-#endif
-
 namespace {
+
+// One workgroup's (batch, head, row-block) and the first Q / K / V row of that head.  1-D grid, XCD-aware: the nblk row-blocks of one
+// (batch, head) get consecutive ids inside ONE XCD's chunk, so the tiles they all stream (K/V in fwd and dQ, Q/dO in dK/dV) are
+// fetched into that XCD's L2 once instead of once per XCD.  Returned BY VALUE: the fields are scalars the kernels keep in SGPRs.
+struct HeadPtrs {
+    int b, h, blk;
+    int64_t rs, ors;                 // row strides (elements) of qkv [B, L, 3, H, HD] and of o / dO [B, Lq, H, HD]
+    const bf16_t *qb, *kb, *vb;
+};
+template <int HD>
+__device__ __forceinline__ HeadPtrs head_ptrs(const bf16_t* __restrict__ qkv, int L, int H, int nblk) {
+    HeadPtrs p;
+    const int sid = xcd_remap(blockIdx.x, gridDim.x);
+    const int bh = sid / nblk;
+    p.blk = sid - bh * nblk;
+    p.b = bh / H;
+    p.h = bh % H;
+    p.rs = (int64_t)3 * H * HD;
+    p.ors = (int64_t)H * HD;
+    p.qb = qkv + (int64_t)p.b * L * p.rs + (int64_t)p.h * HD;
+    p.kb = p.qb + p.ors;
+    p.vb = p.kb + p.ors;
+    return p;
+}
+
+// K and V tile t into LDS buffer `buf` ([buffer 0: K | V][buffer 1: K | V]) for the forward and dQ sweeps
+template <int HD>
+__device__ __forceinline__ void stage_kv(const HeadPtrs hp, const unsigned (&soff)[AG<HD>::CH / 4], int t, int buf, int nfull, int L, unsigned sbase,
+                                         int tid, int wave) {
+    constexpr int TILE = AG<HD>::TILE;
+    const unsigned lds = sbase + buf * 2 * TILE;
+    if (t < nfull) {              // a full tile: scalar base + invariant lane offsets
+        const bf16_t* kt = hp.kb + (int64_t)t * 64 * hp.rs;
+        stage64_full<HD>(kt, soff, lds, wave);
+        stage64_full<HD>(kt + hp.ors, soff, lds + TILE, wave);
+    } else {                      // the ragged last tile: clamped rows
+        stage64<HD>(hp.kb, hp.rs, t * 64, L, lds, tid, wave);
+        stage64<HD>(hp.vb, hp.rs, t * 64, L, lds + TILE, tid, wave);
+    }
+}
+
+// The double-buffered sweep of all three kernels over the streamed tiles t0 .. nt-1 (the first nfull of them full 64-row tiles, at most
+// one ragged tile behind them).  The caller has staged tile t0 into buffer 0 and published it; here tile t sits in buffer (t - t0) & 1,
+// tile t + 1 is staged while t computes, and one dma_drain + barrier per tile publishes it.  body(ragged, buf, t) is one tile's math.
+//   plain : hot loop over full tiles only; the ragged last tile (L % 64 != 0) runs once, after the loop, so its masking code never
+//           shares registers with the steady state.  Two tiles per trip so that the LDS buffer of a tile body is a compile-time
+//           constant (an instruction immediate, not an add).
+//   CAUSAL: every tile goes through body(ragged = true), which itself picks plain / masked / skipped per wave.
+template <bool B>
+struct BoolTag { static constexpr bool value = B; };
+template <bool CAUSAL, class Stage, class Body>
+__device__ __forceinline__ void sweep_tiles(int t0, int nt, int nfull, Stage&& stage, Body&& body) {
+    if constexpr (CAUSAL) {
+        for (int t = t0; t < nt; ++t) {
+            const int cur = (t - t0) & 1;
+            if (t + 1 < nt) stage(t + 1, cur ^ 1);
+            body(BoolTag<true>{}, cur, t);
+            dma_drain();
+            __syncthreads();
+        }
+    } else {
+        for (int t = t0; t < nfull; t += 2) {
+            if (t + 1 < nt) stage(t + 1, 1);
+            body(BoolTag<false>{}, 0, t);
+            dma_drain();
+            __syncthreads();
+            if (t + 1 < nfull) {
+                if (t + 2 < nt) stage(t + 2, 0);
+                body(BoolTag<false>{}, 1, t + 1);
+                dma_drain();
+                __syncthreads();
+            }
+        }
+        if (nfull < nt) body(BoolTag<true>{}, (nfull - t0) & 1, nfull);
+    }
+}
 
 // one 64-key tile of the forward: S^T = K.Q^T, online softmax (log2 domain; max taken on the raw scores since
 // the scale is positive), O^T += V^T.P^T.  TAIL masks keys >= L (last tile of a ragged sequence only).
@@ -135,23 +185,15 @@ __global__ __launch_bounds__(256, CAUSAL ? 3 : 4) void attn_fwd_kernel(const bf1
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int half = lane >> 5;
-    // 1-D grid, XCD-aware: the nblk row-blocks of one (batch, head) get consecutive ids inside ONE XCD's chunk, so the
-    // K/V tiles they all stream are fetched into that XCD's L2 once instead of once per XCD
-    const int sid = xcd_remap(blockIdx.x, gridDim.x);
-    const int bh = sid / nblk, blk = sid - bh * nblk;
-    const int b = bh / H, h = bh % H;
-    const int64_t rs = (int64_t)3 * H * HD;
-    const bf16_t* qb = qkv + (int64_t)b * L * rs + (int64_t)h * HD;
-    const bf16_t* kb = qb + (int64_t)H * HD;
-    const bf16_t* vb = kb + (int64_t)H * HD;
+    const HeadPtrs hp = head_ptrs<HD>(qkv, L, H, nblk);
     // queries q_begin .. L-1 only (q_begin > 0: the last block of a stack, whose other output rows nobody reads); their
     // outputs go to a COMPACT o [B, L - q_begin, H, HD]; keys are always all L rows; lse2 keeps the full [B, H, L] index
-    const int q0 = q_begin + blk * 128 + wave * 32;
+    const int q0 = q_begin + hp.blk * 128 + wave * 32;
     const int Lq = L - q_begin;
 
     constexpr int TILE = AG<HD>::TILE, KS = AG<HD>::KS, DT = AG<HD>::DT;
     bf16x8 qf[KS];
-    load_own<KS>(qb, rs, q0, L, lane, qf);
+    load_own<KS>(hp.qb, hp.rs, q0, L, lane, qf);
 
     f32x16 oacc[DT];
 #pragma unroll
@@ -160,89 +202,32 @@ __global__ __launch_bounds__(256, CAUSAL ? 3 : 4) void attn_fwd_kernel(const bf1
         for (int r = 0; r < 16; ++r) oacc[dt][r] = 0.f;
     float m = -__builtin_inff(), lsum = 0.f;
 
-    const int nt = (L + 63) / 64;
-    // LDS: [buffer 0: K | V][buffer 1: K | V]
+    const int nt = (L + 63) / 64, nfull = (L & 63) ? nt - 1 : nt;
     const unsigned sbase = __builtin_amdgcn_readfirstlane(lds_addr_of(smem));
     const TileAddr<HD> ad = tile_addr<HD>(lane, sbase);
-    stage64<HD>(kb, rs, 0, L, sbase, tid, wave);
-    stage64<HD>(vb, rs, 0, L, sbase + TILE, tid, wave);
+    unsigned soff[AG<HD>::CH / 4];
+    stage_offsets<HD>(hp.rs, tid, soff);
+    auto stage = [&](int t, int buf) __attribute__((always_inline)) { stage_kv<HD>(hp, soff, t, buf, nfull, L, sbase, tid, wave); };
+    stage(0, 0);
     pin_loaded(qf);
     dma_drain();
     __syncthreads();
 
-    // hot loop: full 64-key tiles only; a ragged last tile (L % 64 != 0) runs once, after the loop, so its masking
-    // code never shares registers with the steady state
-    const int nfull = (L & 63) ? nt - 1 : nt;
-    unsigned soff[AG<HD>::CH / 4];
-    stage_offsets<HD>(rs, tid, soff);
-    if constexpr (CAUSAL) {
-        const int q_end = min(L, q_begin + blk * 128 + 128);            // one past the workgroup's last query
-        const int nt_c = min(nt, (q_end + 63) / 64);                    // tiles any of its queries can see
-        const int nvis = min(nfull, (q0 + 1) / 64);                     // tiles with every key <= the wave's first query
-        const int lim = min(L, q0 + (lane & 31) + 1);                   // this lane's query sees keys < lim
-        for (int t = 0; t < nt_c; ++t) {
-            const int cur = t & 1;
-            if (t + 1 < nt_c) {
-                if (t + 1 < nfull) {
-                    const bf16_t* kt = kb + (int64_t)(t + 1) * 64 * rs;
-                    stage64_full<HD>(kt, soff, sbase + (cur ^ 1) * 2 * TILE, wave);
-                    stage64_full<HD>(kt + (int64_t)H * HD, soff, sbase + (cur ^ 1) * 2 * TILE + TILE, wave);
-                } else {
-                    stage64<HD>(kb, rs, (t + 1) * 64, L, sbase + (cur ^ 1) * 2 * TILE, tid, wave);
-                    stage64<HD>(vb, rs, (t + 1) * 64, L, sbase + (cur ^ 1) * 2 * TILE + TILE, tid, wave);
-                }
-            }
-            const unsigned kl = cur * 2 * TILE;
-            if (t < nvis) fwd_tile<HD, false>(kl, kl + TILE, ad, qf, oacc, m, lsum, t * 64, L, scale_log2e, half);
-            else if (t * 64 <= q0 + 31) fwd_tile<HD, true>(kl, kl + TILE, ad, qf, oacc, m, lsum, t * 64, lim, scale_log2e, half);
-            dma_drain();
-            __syncthreads();
-        }
-    } else {
-    // two tiles per trip so that the LDS buffer of a tile body is a compile-time constant (an instruction immediate, not an add)
-    auto stage_next = [&](int t, int cur) {   // tile t + 1 into the other buffer
-        if (t + 1 < nfull) {          // next tile is a full one: scalar base + invariant lane offsets
-            const bf16_t* kt = kb + (int64_t)(t + 1) * 64 * rs;
-            stage64_full<HD>(kt, soff, sbase + (cur ^ 1) * 2 * TILE, wave);
-            stage64_full<HD>(kt + (int64_t)H * HD, soff, sbase + (cur ^ 1) * 2 * TILE + TILE, wave);
-        } else if (t + 1 < nt) {      // the ragged last tile: clamped rows
-            stage64<HD>(kb, rs, (t + 1) * 64, L, sbase + (cur ^ 1) * 2 * TILE, tid, wave);
-            stage64<HD>(vb, rs, (t + 1) * 64, L, sbase + (cur ^ 1) * 2 * TILE + TILE, tid, wave);
-        }
-    };
-    VT_STAMP_DECL;
-    for (int t = 0; t < nfull; t += 2) {
-        VT_STAMP_START;
-        stage_next(t, 0);
-        fwd_tile<HD, false>(0, TILE, ad, qf, oacc, m, lsum, t * 64, L, scale_log2e, half);
-        VT_STAMP(0);
-        dma_drain();
-        VT_STAMP(1);
-        __syncthreads();
-        VT_STAMP(2);
-        VT_STAMP_ITER;
-        if (t + 1 < nfull) {
-            stage_next(t + 1, 1);
-            fwd_tile<HD, false>(2 * TILE, 3 * TILE, ad, qf, oacc, m, lsum, (t + 1) * 64, L, scale_log2e, half);
-            VT_STAMP(0);
-            dma_drain();
-            VT_STAMP(1);
-            __syncthreads();
-            VT_STAMP(2);
-            VT_STAMP_ITER;
-        }
-    }
-    VT_STAMP_FLUSH(0);
-    if (nfull < nt) {
-        const unsigned kl = (nfull & 1) * 2 * TILE;
-        fwd_tile<HD, true>(kl, kl + TILE, ad, qf, oacc, m, lsum, nfull * 64, L, scale_log2e, half);
-    }
-    }
+    const int q_end = min(L, q_begin + hp.blk * 128 + 128);           // one past the workgroup's last query
+    const int nt_c = CAUSAL ? min(nt, (q_end + 63) / 64) : nt;        // CAUSAL: tiles any of its queries can see
+    const int nvis = min(nfull, (q0 + 1) / 64);                       // CAUSAL: tiles with every key <= the wave's first query
+    const int lim = min(L, q0 + (lane & 31) + 1);                     // CAUSAL: this lane's query sees keys < lim
+    sweep_tiles<CAUSAL>(0, nt_c, nfull, stage, [&](auto ragged, int buf, int t) __attribute__((always_inline)) {
+        const unsigned kl = buf * 2 * TILE;
+        if constexpr (!CAUSAL) fwd_tile<HD, decltype(ragged)::value>(kl, kl + TILE, ad, qf, oacc, m, lsum, t * 64, L, scale_log2e, half);
+        else if (t < nvis) fwd_tile<HD, false>(kl, kl + TILE, ad, qf, oacc, m, lsum, t * 64, L, scale_log2e, half);
+        else if (t * 64 <= q0 + 31) fwd_tile<HD, true>(kl, kl + TILE, ad, qf, oacc, m, lsum, t * 64, lim, scale_log2e, half);
+    });
     const float ltot = lsum + __shfl_xor(lsum, 32);
     const int q = q0 + (lane & 31);
     const bool ok = q < L;
-    store_own<DT>(oacc, 1.0f / ltot, o + (int64_t)b * Lq * H * HD + (int64_t)h * HD, (int64_t)H * HD, q - q_begin, ok, half);
-    if (ok && half == 0) lse2[((int64_t)b * H + h) * L + q] = m + __builtin_amdgcn_logf(ltot);  // v_log_f32 = log2
+    store_own<DT>(oacc, 1.0f / ltot, o + (int64_t)hp.b * Lq * hp.ors + (int64_t)hp.h * HD, hp.ors, q - q_begin, ok, half);
+    if (ok && half == 0) lse2[((int64_t)hp.b * H + hp.h) * L + q] = m + __builtin_amdgcn_logf(ltot);  // v_log_f32 = log2
 }
 
 template <int HD, bool TAIL>
@@ -295,33 +280,27 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(const bf16_t* __res
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int half = lane >> 5;
-    const int sid = xcd_remap(blockIdx.x, gridDim.x);  // see attn_fwd_kernel
-    const int bh = sid / nblk, blk = sid - bh * nblk;
-    const int b = bh / H, h = bh % H;
-    const int64_t rs = (int64_t)3 * H * HD, ors = (int64_t)H * HD;
-    const bf16_t* qb = qkv + (int64_t)b * L * rs + (int64_t)h * HD;
-    const bf16_t* kb = qb + (int64_t)H * HD;
-    const bf16_t* vb = kb + (int64_t)H * HD;
-    const int q0 = q_begin + blk * 128 + wave * 32;   // kept queries only; o / dO are compact [B, L - q_begin, H, HD]
+    const HeadPtrs hp = head_ptrs<HD>(qkv, L, H, nblk);
+    const int q0 = q_begin + hp.blk * 128 + wave * 32;   // kept queries only; o / dO are compact [B, L - q_begin, H, HD]
     const int Lq = L - q_begin;
     const int q = q0 + (lane & 31);
     const int qc = q < L ? q : L - 1;
 
     constexpr int TILE = AG<HD>::TILE, KS = AG<HD>::KS, DT = AG<HD>::DT;
     bf16x8 qf[KS], dof[KS];
-    load_own<KS>(qb, rs, q0, L, lane, qf);
-    load_own<KS>(dO + (int64_t)b * Lq * ors + (int64_t)h * HD, ors, q0 - q_begin, Lq, lane, dof);
-    const float my_lse = lse2[((int64_t)b * H + h) * L + qc];
+    load_own<KS>(hp.qb, hp.rs, q0, L, lane, qf);
+    load_own<KS>(dO + (int64_t)hp.b * Lq * hp.ors + (int64_t)hp.h * HD, hp.ors, q0 - q_begin, Lq, lane, dof);
+    const float my_lse = lse2[((int64_t)hp.b * H + hp.h) * L + qc];
     float my_delta = 0.f;
     {
         bf16x8 of[KS];
-        load_own<KS>(o + (int64_t)b * Lq * ors + (int64_t)h * HD, ors, q0 - q_begin, Lq, lane, of);
+        load_own<KS>(o + (int64_t)hp.b * Lq * hp.ors + (int64_t)hp.h * HD, hp.ors, q0 - q_begin, Lq, lane, of);
 #pragma unroll
         for (int s = 0; s < KS; ++s)
 #pragma unroll
             for (int j = 0; j < 8; ++j) my_delta += bf2f(of[s][j]) * bf2f(dof[s][j]);
         my_delta += __shfl_xor(my_delta, 32);   // the two lane halves hold the two halves of every 16-wide k-step
-        if (q < L && half == 0) delta[((int64_t)b * H + h) * L + q] = my_delta;
+        if (q < L && half == 0) delta[((int64_t)hp.b * H + hp.h) * L + q] = my_delta;
     }
 
     f32x16 dq[DT];
@@ -330,12 +309,13 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(const bf16_t* __res
 #pragma unroll
         for (int r = 0; r < 16; ++r) dq[dt][r] = 0.f;
 
-    const int nt = (L + 63) / 64;
-    // LDS: [buffer 0: K | V][buffer 1: K | V]
+    const int nt = (L + 63) / 64, nfull = (L & 63) ? nt - 1 : nt;
     const unsigned sbase = __builtin_amdgcn_readfirstlane(lds_addr_of(smem));
     const TileAddr<HD> ad = tile_addr<HD>(lane, sbase);
-    stage64<HD>(kb, rs, 0, L, sbase, tid, wave);
-    stage64<HD>(vb, rs, 0, L, sbase + TILE, tid, wave);
+    unsigned soff[AG<HD>::CH / 4];
+    stage_offsets<HD>(hp.rs, tid, soff);
+    auto stage = [&](int t, int buf) __attribute__((always_inline)) { stage_kv<HD>(hp, soff, t, buf, nfull, L, sbase, tid, wave); };
+    stage(0, 0);
     pin_loaded(qf);
     pin_loaded(dof);
     float lse_pin = my_lse;
@@ -344,72 +324,17 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(const bf16_t* __res
     dma_drain();
     __syncthreads();
 
-    const int nfull = (L & 63) ? nt - 1 : nt;
-    unsigned soff[AG<HD>::CH / 4];
-    stage_offsets<HD>(rs, tid, soff);
-    if constexpr (CAUSAL) {   // see attn_fwd_kernel
-        const int q_end = min(L, q_begin + blk * 128 + 128);
-        const int nt_c = min(nt, (q_end + 63) / 64);
-        const int nvis = min(nfull, (q0 + 1) / 64);
-        const int lim = min(L, q0 + (lane & 31) + 1);
-        for (int t = 0; t < nt_c; ++t) {
-            const int cur = t & 1;
-            if (t + 1 < nt_c) {
-                if (t + 1 < nfull) {
-                    const bf16_t* kt = kb + (int64_t)(t + 1) * 64 * rs;
-                    stage64_full<HD>(kt, soff, sbase + (cur ^ 1) * 2 * TILE, wave);
-                    stage64_full<HD>(kt + (int64_t)H * HD, soff, sbase + (cur ^ 1) * 2 * TILE + TILE, wave);
-                } else {
-                    stage64<HD>(kb, rs, (t + 1) * 64, L, sbase + (cur ^ 1) * 2 * TILE, tid, wave);
-                    stage64<HD>(vb, rs, (t + 1) * 64, L, sbase + (cur ^ 1) * 2 * TILE + TILE, tid, wave);
-                }
-            }
-            const unsigned kl = cur * 2 * TILE;
-            if (t < nvis) dq_tile<HD, false>(kl, kl + TILE, ad, qf, dof, dq, lse_pin, my_delta, t * 64, L, scale_log2e, half);
-            else if (t * 64 <= q0 + 31) dq_tile<HD, true>(kl, kl + TILE, ad, qf, dof, dq, lse_pin, my_delta, t * 64, lim, scale_log2e, half);
-            dma_drain();
-            __syncthreads();
-        }
-    } else {
-    auto stage_next = [&](int t, int cur) {   // tile t + 1 into the other buffer
-        if (t + 1 < nfull) {
-            const bf16_t* kt = kb + (int64_t)(t + 1) * 64 * rs;
-            stage64_full<HD>(kt, soff, sbase + (cur ^ 1) * 2 * TILE, wave);
-            stage64_full<HD>(kt + (int64_t)H * HD, soff, sbase + (cur ^ 1) * 2 * TILE + TILE, wave);
-        } else if (t + 1 < nt) {
-            stage64<HD>(kb, rs, (t + 1) * 64, L, sbase + (cur ^ 1) * 2 * TILE, tid, wave);
-            stage64<HD>(vb, rs, (t + 1) * 64, L, sbase + (cur ^ 1) * 2 * TILE + TILE, tid, wave);
-        }
-    };
-    VT_STAMP_DECL;
-    for (int t = 0; t < nfull; t += 2) {      // two tiles per trip: the LDS buffer of a body is an instruction immediate
-        VT_STAMP_START;
-        stage_next(t, 0);
-        dq_tile<HD, false>(0, TILE, ad, qf, dof, dq, lse_pin, my_delta, t * 64, L, scale_log2e, half);
-        VT_STAMP(0);
-        dma_drain();
-        VT_STAMP(1);
-        __syncthreads();
-        VT_STAMP(2);
-        VT_STAMP_ITER;
-        if (t + 1 < nfull) {
-            stage_next(t + 1, 1);
-            dq_tile<HD, false>(2 * TILE, 3 * TILE, ad, qf, dof, dq, lse_pin, my_delta, (t + 1) * 64, L, scale_log2e, half);
-            VT_STAMP(0);
-            dma_drain();
-            VT_STAMP(1);
-            __syncthreads();
-            VT_STAMP(2);
-            VT_STAMP_ITER;
-        }
-    }
-    VT_STAMP_FLUSH(1);
-    if (nfull < nt) {
-        const unsigned kl = (nfull & 1) * 2 * TILE;
-        dq_tile<HD, true>(kl, kl + TILE, ad, qf, dof, dq, lse_pin, my_delta, nfull * 64, L, scale_log2e, half);
-    }
-    }
-    store_own<DT>(dq, scale, dqkv + (int64_t)b * L * rs + (int64_t)h * HD, rs, q, q < L, half);
+    const int q_end = min(L, q_begin + hp.blk * 128 + 128);           // CAUSAL: see attn_fwd_kernel
+    const int nt_c = CAUSAL ? min(nt, (q_end + 63) / 64) : nt;
+    const int nvis = min(nfull, (q0 + 1) / 64);
+    const int lim = min(L, q0 + (lane & 31) + 1);
+    sweep_tiles<CAUSAL>(0, nt_c, nfull, stage, [&](auto ragged, int buf, int t) __attribute__((always_inline)) {
+        const unsigned kl = buf * 2 * TILE;
+        if constexpr (!CAUSAL) dq_tile<HD, decltype(ragged)::value>(kl, kl + TILE, ad, qf, dof, dq, lse_pin, my_delta, t * 64, L, scale_log2e, half);
+        else if (t < nvis) dq_tile<HD, false>(kl, kl + TILE, ad, qf, dof, dq, lse_pin, my_delta, t * 64, L, scale_log2e, half);
+        else if (t * 64 <= q0 + 31) dq_tile<HD, true>(kl, kl + TILE, ad, qf, dof, dq, lse_pin, my_delta, t * 64, lim, scale_log2e, half);
+    });
+    store_own<DT>(dq, scale, dqkv + (int64_t)hp.b * L * hp.rs + (int64_t)hp.h * HD, hp.rs, q, q < L, half);
 }
 
 // one 64-query tile of the dK/dV sweep.  LDS buffer: Q tile | dO tile | lse2[64] | delta[64]
@@ -481,25 +406,20 @@ __global__ __launch_bounds__(256, CAUSAL ? 2 : 3) void attn_bwd_dkv_kernel(const
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int half = lane >> 5;
-    const int sid = xcd_remap(blockIdx.x, gridDim.x);  // key blocks of one head share the Q/dO stream: keep them on one XCD
-    const int bh = sid / nblk, blk = sid - bh * nblk;
-    const int b = bh / H, h = bh % H;
-    const int64_t rs = (int64_t)3 * H * HD, ors = (int64_t)H * HD;
-    const bf16_t* qb = qkv + (int64_t)b * L * rs + (int64_t)h * HD;
-    const bf16_t* kb = qb + (int64_t)H * HD;
-    const bf16_t* vb = kb + (int64_t)H * HD;
+    const HeadPtrs hp = head_ptrs<HD>(qkv, L, H, nblk);
+    const int64_t rs = hp.rs, ors = hp.ors;
     // query tiles from q_begin on (a multiple of 64; the rows before it got no gradient), dO compact [B, L - q_begin, H, HD]
     const int Lq = L - q_begin;
-    const bf16_t* dob = dO + (int64_t)b * Lq * ors + (int64_t)h * HD;
-    const float* lse_b = lse2 + ((int64_t)b * H + h) * L;
-    const float* del_b = delta + ((int64_t)b * H + h) * L;
-    const int k0 = blk * 128 + wave * 32;
+    const bf16_t* dob = dO + (int64_t)hp.b * Lq * ors + (int64_t)hp.h * HD;
+    const float* lse_b = lse2 + ((int64_t)hp.b * H + hp.h) * L;
+    const float* del_b = delta + ((int64_t)hp.b * H + hp.h) * L;
+    const int k0 = hp.blk * 128 + wave * 32;
     const int key = k0 + (lane & 31);
 
     constexpr int TILE = AG<HD>::TILE, KS = AG<HD>::KS, DT = AG<HD>::DT;
     bf16x8 kf[KS], vf[KS];
-    load_own<KS>(kb, rs, k0, L, lane, kf);
-    load_own<KS>(vb, rs, k0, L, lane, vf);
+    load_own<KS>(hp.kb, rs, k0, L, lane, kf);
+    load_own<KS>(hp.vb, rs, k0, L, lane, vf);
 
     f32x16 dk[DT], dv[DT];
 #pragma unroll
@@ -509,7 +429,7 @@ __global__ __launch_bounds__(256, CAUSAL ? 2 : 3) void attn_bwd_dkv_kernel(const
 
     // LDS: per buffer  Q tile | dO tile | lse2[64] | delta[64]
     constexpr int BUF = 2 * TILE + 512;
-    const int nt = (L + 63) / 64;
+    const int nt = (L + 63) / 64, nfull = (L & 63) ? nt - 1 : nt;
     const unsigned sbase = __builtin_amdgcn_readfirstlane(lds_addr_of(smem));
     const TileAddr<HD> ad = tile_addr<HD>(lane, sbase);
     unsigned lse_a = sbase + 16 * half;
@@ -518,13 +438,13 @@ __global__ __launch_bounds__(256, CAUSAL ? 2 : 3) void attn_bwd_dkv_kernel(const
     stage_offsets<HD>(rs, tid, qoff);
     stage_offsets<HD>(ors, tid, dooff);
     const int nfull_q = L / 64;        // query tiles without a ragged row
-    auto stage = [&](int t, int buf) {
+    auto stage = [&](int t, int buf) __attribute__((always_inline)) {
         const unsigned base = sbase + buf * BUF;
         if (t < nfull_q) {
-            stage64_full<HD>(qb + (int64_t)t * 64 * rs, qoff, base, wave);
+            stage64_full<HD>(hp.qb + (int64_t)t * 64 * rs, qoff, base, wave);
             stage64_full<HD>(dob + ((int64_t)t * 64 - q_begin) * ors, dooff, base + TILE, wave);
         } else {
-            stage64<HD>(qb, rs, t * 64, L, base, tid, wave);
+            stage64<HD>(hp.qb, rs, t * 64, L, base, tid, wave);
             stage64<HD>(dob, ors, t * 64 - q_begin, Lq, base + TILE, tid, wave);
         }
         if (wave < 2) {  // wave 0: lse2[64], wave 1: delta[64] by 4-byte LDS-DMA (rows past L clamped; masked at use)
@@ -534,52 +454,21 @@ __global__ __launch_bounds__(256, CAUSAL ? 2 : 3) void attn_bwd_dkv_kernel(const
         }
     };
     // CAUSAL: query tiles before the workgroup's first key contribute nothing (every query < every key)
-    const int t0 = CAUSAL ? max(q_begin >> 6, (blk * 128) >> 6) : q_begin >> 6;
+    const int t0 = CAUSAL ? max(q_begin >> 6, (hp.blk * 128) >> 6) : q_begin >> 6;
     stage(t0, 0);
     pin_loaded(kf);
     pin_loaded(vf);
     dma_drain();
     __syncthreads();
 
-    const int nfull = (L & 63) ? nt - 1 : nt;
-    if constexpr (CAUSAL) {
-        for (int t = t0; t < nt; ++t) {
-            const int cur = (t - t0) & 1;
-            if (t + 1 < nt) stage(t + 1, cur ^ 1);
-            if (t < nfull && t * 64 >= k0 + 31) dkv_tile<HD, false>(cur * BUF, lse_a, ad, kf, vf, dk, dv, t * 64, L, scale_log2e, half);
-            else if (t * 64 + 63 >= k0) dkv_tile<HD, true, true>(cur * BUF, lse_a, ad, kf, vf, dk, dv, t * 64, L, scale_log2e, half, key);
-            dma_drain();
-            __syncthreads();
-        }
-    } else {
-    VT_STAMP_DECL;
-    for (int t = t0; t < nfull; t += 2) {     // two tiles per trip: the LDS buffer of a body is an instruction immediate
-        VT_STAMP_START;
-        if (t + 1 < nt) stage(t + 1, 1);
-        dkv_tile<HD, false>(0, lse_a, ad, kf, vf, dk, dv, t * 64, L, scale_log2e, half);
-        VT_STAMP(0);
-        dma_drain();
-        VT_STAMP(1);
-        __syncthreads();
-        VT_STAMP(2);
-        VT_STAMP_ITER;
-        if (t + 1 < nfull) {
-            if (t + 2 < nt) stage(t + 2, 0);
-            dkv_tile<HD, false>(BUF, lse_a, ad, kf, vf, dk, dv, (t + 1) * 64, L, scale_log2e, half);
-            VT_STAMP(0);
-            dma_drain();
-            VT_STAMP(1);
-            __syncthreads();
-            VT_STAMP(2);
-            VT_STAMP_ITER;
-        }
-    }
-    VT_STAMP_FLUSH(2);
-    if (nfull < nt) dkv_tile<HD, true>(((nfull - t0) & 1) * BUF, lse_a, ad, kf, vf, dk, dv, nfull * 64, L, scale_log2e, half);
-    }
-    bf16_t* dkb = dqkv + (int64_t)b * L * rs + (int64_t)h * HD + (int64_t)H * HD;
+    sweep_tiles<CAUSAL>(t0, nt, nfull, stage, [&](auto ragged, int buf, int t) __attribute__((always_inline)) {
+        if constexpr (!CAUSAL) dkv_tile<HD, decltype(ragged)::value>(buf * BUF, lse_a, ad, kf, vf, dk, dv, t * 64, L, scale_log2e, half);
+        else if (t < nfull && t * 64 >= k0 + 31) dkv_tile<HD, false>(buf * BUF, lse_a, ad, kf, vf, dk, dv, t * 64, L, scale_log2e, half);
+        else if (t * 64 + 63 >= k0) dkv_tile<HD, true, true>(buf * BUF, lse_a, ad, kf, vf, dk, dv, t * 64, L, scale_log2e, half, key);
+    });
+    bf16_t* dkb = dqkv + (int64_t)hp.b * L * rs + (int64_t)hp.h * HD + ors;
     store_own<DT>(dk, scale, dkb, rs, key, key < L, half);
-    store_own<DT>(dv, 1.0f, dkb + (int64_t)H * HD, rs, key, key < L, half);
+    store_own<DT>(dv, 1.0f, dkb + ors, rs, key, key < L, half);
 }
 
 // dQ rows of the queries before q_begin: they received no gradient (the dQ kernel only visits the kept queries)
@@ -597,26 +486,31 @@ __global__ void zero_q_rows_kernel(bf16_t* __restrict__ dqkv, int L, int q_begin
 
 }  // namespace
 
+// softmax scale 1 / sqrt(HD), and the same times log2(e) for the exp2-domain kernels
 template <int HD>
+constexpr float kScale = HD == 64 ? 0.125f : 0.17677669529663688110f;
+template <int HD>
+constexpr float kScaleLog2e = kScale<HD> * 1.44269504088896340736f;
+
+template <int HD, bool CAUSAL = false>
 static void launch_fwd(const void* qkv, int B, int L, int H, int q_begin, void* o, float* lse2, hipStream_t s) {
-    const float sl2 = (HD == 64 ? 0.125f : 0.17677669529663688110f) * 1.44269504088896340736f;
     const int nblk = (L - q_begin + 127) / 128;
-    hipLaunchKernelGGL(attn_fwd_kernel<HD>, dim3(nblk * B * H), dim3(256), 4 * AG<HD>::TILE, s, (const bf16_t*)qkv, (bf16_t*)o, lse2, L, H, nblk, sl2, q_begin);
+    hipLaunchKernelGGL((attn_fwd_kernel<HD, CAUSAL>), dim3(nblk * B * H), dim3(256), 4 * AG<HD>::TILE, s, (const bf16_t*)qkv, (bf16_t*)o, lse2, L, H, nblk,
+                       kScaleLog2e<HD>, q_begin);
 }
 
-template <int HD>
+template <int HD, bool CAUSAL = false>
 static void launch_bwd(const void* qkv, const void* o, const void* dO, const float* lse2, int B, int L, int H, int q_begin, void* dqkv,
                        float* delta_ws, hipStream_t s) {
-    const float scale = HD == 64 ? 0.125f : 0.17677669529663688110f, sl2 = scale * 1.44269504088896340736f;
     if (q_begin > 0) {
         const int64_t n = (int64_t)B * q_begin * (H * HD / 8);
         hipLaunchKernelGGL(zero_q_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (bf16_t*)dqkv, L, q_begin, (int64_t)3 * H * HD, H * HD);
     }
     const int nblk_q = (L - q_begin + 127) / 128, nblk_k = (L + 127) / 128;
-    hipLaunchKernelGGL(attn_bwd_dq_kernel<HD>, dim3(nblk_q * B * H), dim3(256), 4 * AG<HD>::TILE, s, (const bf16_t*)qkv, (const bf16_t*)o, (const bf16_t*)dO, lse2,
-                       delta_ws, (bf16_t*)dqkv, L, H, nblk_q, scale, sl2, q_begin);
-    hipLaunchKernelGGL(attn_bwd_dkv_kernel<HD>, dim3(nblk_k * B * H), dim3(256), 2 * (2 * AG<HD>::TILE + 512), s, (const bf16_t*)qkv, (const bf16_t*)dO, lse2,
-                       delta_ws, (bf16_t*)dqkv, L, H, nblk_k, scale, sl2, q_begin);
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<HD, CAUSAL>), dim3(nblk_q * B * H), dim3(256), 4 * AG<HD>::TILE, s, (const bf16_t*)qkv, (const bf16_t*)o,
+                       (const bf16_t*)dO, lse2, delta_ws, (bf16_t*)dqkv, L, H, nblk_q, kScale<HD>, kScaleLog2e<HD>, q_begin);
+    hipLaunchKernelGGL((attn_bwd_dkv_kernel<HD, CAUSAL>), dim3(nblk_k * B * H), dim3(256), 2 * (2 * AG<HD>::TILE + 512), s, (const bf16_t*)qkv,
+                       (const bf16_t*)dO, lse2, delta_ws, (bf16_t*)dqkv, L, H, nblk_k, kScale<HD>, kScaleLog2e<HD>, q_begin);
 }
 
 // every operand is read and every output written 16 bytes per lane (the outputs since the widened stores of round 5)
@@ -664,7 +558,6 @@ extern "C" int vt_attention_bwd(const void* qkv, const void* o, const void* dO, 
     return vt_attention_bwd_rows(qkv, o, dO, lse2, B, L, H, hd, 0, dqkv, delta_ws, stream);
 }
 
-
 // ------------------------------------------------------------------------------------------------
 // causal attention (the AR consumer): F.scaled_dot_product_attention(q, k, v, is_causal=True) of
 // /root/reference/models/larp_ar.py:186-190 and its autograd; head_dim 64 (every llama-abs size: dim / n_head = 64)
@@ -673,10 +566,7 @@ extern "C" int vt_attention_causal_fwd(const void* qkv, int32_t B, int32_t L, in
     VT_CHECK_ARG(qkv && o && lse2, "vt_attention_causal_fwd: null pointer");
     VT_CHECK_ARG(B > 0 && L > 0 && H > 0, "vt_attention_causal_fwd: bad shape");
     VT_CHECK_ARG(attn_aligned(qkv, o), "vt_attention_causal_fwd: qkv and o must be 16-byte aligned");
-    const float sl2 = 0.125f * 1.44269504088896340736f;
-    const int nblk = (L + 127) / 128;
-    hipLaunchKernelGGL((attn_fwd_kernel<64, true>), dim3(nblk * B * H), dim3(256), 4 * AG<64>::TILE, (hipStream_t)stream, (const bf16_t*)qkv, (bf16_t*)o, lse2, L, H,
-                       nblk, sl2, 0);
+    launch_fwd<64, true>(qkv, B, L, H, 0, o, lse2, (hipStream_t)stream);
     VT_CHECK_LAUNCH("vt_attention_causal_fwd");
     return VT_OK;
 }
@@ -686,19 +576,7 @@ extern "C" int vt_attention_causal_bwd(const void* qkv, const void* o, const voi
     VT_CHECK_ARG(qkv && o && dO && lse2 && dqkv && delta_ws, "vt_attention_causal_bwd: null pointer");
     VT_CHECK_ARG(B > 0 && L > 0 && H > 0, "vt_attention_causal_bwd: bad shape");
     VT_CHECK_ARG(attn_aligned(qkv, o, dO, dqkv), "vt_attention_causal_bwd: qkv, o, dO and dqkv must be 16-byte aligned");
-    const float scale = 0.125f, sl2 = scale * 1.44269504088896340736f;
-    const int nblk = (L + 127) / 128;
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<64, true>), dim3(nblk * B * H), dim3(256), 4 * AG<64>::TILE, s, (const bf16_t*)qkv, (const bf16_t*)o, (const bf16_t*)dO,
-                       lse2, delta_ws, (bf16_t*)dqkv, L, H, nblk, scale, sl2, 0);
-    hipLaunchKernelGGL((attn_bwd_dkv_kernel<64, true>), dim3(nblk * B * H), dim3(256), 2 * (2 * AG<64>::TILE + 512), s, (const bf16_t*)qkv, (const bf16_t*)dO, lse2,
-                       delta_ws, (bf16_t*)dqkv, L, H, nblk, scale, sl2, 0);
+    launch_bwd<64, true>(qkv, o, dO, lse2, B, L, H, 0, dqkv, delta_ws, (hipStream_t)stream);
     VT_CHECK_LAUNCH("vt_attention_causal_bwd");
     return VT_OK;
 }
-
-#ifdef VT_ATTN_STAMPS
-extern "C" int vt_attention_stamps(unsigned long long* host_out) {   // diagnostic build only: 3 x 2048 x 4 x 6 counters
-    return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_attn_stamps), sizeof(g_attn_stamps)) == hipSuccess ? VT_OK : VT_ERR_LAUNCH;
-}
-#endif

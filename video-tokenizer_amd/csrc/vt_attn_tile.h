@@ -1,11 +1,10 @@
-// Tile-level helpers shared by the attention kernels (vt_attention.hip, vt_attention_bwd.hip): the [64][HD] bf16 LDS tile image,
+// Tile-level helpers shared by the attention kernels (vt_attention.hip: forward, dQ, dK/dV): the [64][HD] bf16 LDS tile image,
 // its swizzle, LDS-DMA staging, the row / transposed MFMA fragments and the accumulator-as-operand packing.  See the header
 // comment of vt_attention.hip for the layout and the k-order convention.
 #pragma once
 #include "vt_common.h"
 
 namespace {
-
 
 template <int HD>
 struct AG {
@@ -53,29 +52,6 @@ template <int HD>
 __device__ __forceinline__ void stage64_full(const bf16_t* tile_row0, const unsigned (&off)[AG<HD>::CH / 4], unsigned lds, int wave) {
 #pragma unroll
     for (int i = 0; i < AG<HD>::CH / 4; ++i) glds16_sv(tile_row0, off[i], lds + (i * 256 + wave * 64) * 16);
-}
-
-// A operand of a 32x32x16 MFMA from tile rows r0..r0+31, k-step s (16 columns)
-template <int HD>
-__device__ __forceinline__ bf16x8 rowfrag(const char* lds, int r0, int s, int lane) {
-    const int row = r0 + (lane & 31);
-    const int lc = 2 * s + (lane >> 5);
-    return *(const bf16x8*)(lds + row * AG<HD>::ROWB + ((lc ^ fsw<HD>(row)) << 4));
-}
-
-// A operand [i = column c0 + (lane&31)][k = tile rows], k order matched to an accumulator used as B:
-// element j  <->  tile row rbase + 16*sp + 8*(j>>2) + 4*(lane>>5) + (j&3)
-template <int HD>
-__device__ __forceinline__ bf16x8 trfrag(const char* lds, int rbase, int sp, int c0, int lane) {
-    const int g = lane >> 4, lam = lane & 15;
-    const int r0 = rbase + 16 * sp + 4 * (g >> 1) + (lam >> 2);
-    const int r1 = r0 + 8;
-    const int cb = c0 + 16 * (g & 1);
-    const int lc = (cb >> 3) + ((lam & 3) >> 1);
-    const int bo = (lam & 1) << 3;
-    const bf16x4 lo = lds_read_tr16(lds + r0 * AG<HD>::ROWB + ((lc ^ fsw<HD>(r0)) << 4) + bo);
-    const bf16x4 hi = lds_read_tr16(lds + r1 * AG<HD>::ROWB + ((lc ^ fsw<HD>(r1)) << 4) + bo);
-    return cat4(lo, hi);
 }
 
 // Round 4: the same two fragments from per-lane byte offsets computed ONCE per kernel.  Everything that depends on the buffer, the tile
@@ -171,42 +147,25 @@ __device__ __forceinline__ int reg_row(int r, int half) { return (r & 3) + 8 * (
 // upper half-wave's group k with the lower one's group k + 1: lanes 0-31 then hold columns 8k .. 8k+7 and lanes 32-63 columns
 // 8k+8 .. 8k+15 of their row -- ONE 16-byte store per pair of groups, same bytes at the same addresses, half the instructions.
 // (every lane takes part in the swaps; `ok` only masks the stores: a row's two lanes are valid or invalid together)
-#ifndef VT_ATTN_STORE8
-#define VT_ATTN_STORE8 0     // A/B diagnostic: 1 = the 8-byte stores of rounds 1-5
-#endif
 template <int DT>
 __device__ __forceinline__ void store_own(const f32x16 (&acc)[DT], float mul, bf16_t* __restrict__ dst, int64_t rs, int row, bool ok, int half) {
-    if constexpr (VT_ATTN_STORE8) {
-        if (!ok) return;
-        bf16_t* p = dst + (int64_t)row * rs;
+    bf16_t* p = dst + (int64_t)row * rs + 8 * half;      // the upper half-wave writes the next 16 bytes of the row
 #pragma unroll
-        for (int dt = 0; dt < DT; ++dt)
+    for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4) {
-                bf16x4 v;
+        for (int k = 0; k < 4; k += 2) {
+            bf16x4 va, vb;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = f2bf(acc[dt][4 * g4 + e] * mul);
-                *(bf16x4*)(p + dt * 32 + 8 * g4 + 4 * half) = v;
+            for (int e = 0; e < 4; ++e) {
+                va[e] = f2bf(acc[dt][4 * k + e] * mul);
+                vb[e] = f2bf(acc[dt][4 * (k + 1) + e] * mul);
             }
-    } else {
-        bf16_t* p = dst + (int64_t)row * rs + 8 * half;      // the upper half-wave writes the next 16 bytes of the row
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-            for (int k = 0; k < 4; k += 2) {
-                bf16x4 va, vb;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    va[e] = f2bf(acc[dt][4 * k + e] * mul);
-                    vb[e] = f2bf(acc[dt][4 * (k + 1) + e] * mul);
-                }
-                u32x2_t a = __builtin_bit_cast(u32x2_t, va), b = __builtin_bit_cast(u32x2_t, vb);
-                const auto r0 = __builtin_amdgcn_permlane32_swap(a[0], b[0], false, false);
-                const auto r1 = __builtin_amdgcn_permlane32_swap(a[1], b[1], false, false);
-                const u32x4_t w = {r0[0], r1[0], r0[1], r1[1]};
-                if (ok) *(u32x4_t*)(p + dt * 32 + 8 * k) = w;
-            }
-    }
+            u32x2_t a = __builtin_bit_cast(u32x2_t, va), b = __builtin_bit_cast(u32x2_t, vb);
+            const auto r0 = __builtin_amdgcn_permlane32_swap(a[0], b[0], false, false);
+            const auto r1 = __builtin_amdgcn_permlane32_swap(a[1], b[1], false, false);
+            const u32x4_t w = {r0[0], r1[0], r0[1], r1[1]};
+            if (ok) *(u32x4_t*)(p + dt * 32 + 8 * k) = w;
+        }
 }
 
 }  // namespace
