@@ -57,7 +57,12 @@ enum {
     VT_EPI_BF16_GELU = 1,  /* out(bf16) = u = acc + bias ; out2(bf16) = gelu_erf(u)           */
     VT_EPI_F32 = 2,        /* out(f32)  = [round_bf16](acc [+ bias]) [+ residual] [+ rowmod]; */
                            /*             optional out2(bf16) copy; optional output row map   */
-    VT_EPI_BF16_DGELU = 3  /* out(bf16) = acc * gelu_erf'(aux)      (aux = saved u, bf16)     */
+    VT_EPI_BF16_DGELU = 3, /* out(bf16) = acc * gelu_erf'(aux)      (aux = saved u, bf16)     */
+    VT_EPI_BF16_GELU_GRAD = 4, /* with u = bf16(acc + bias): out(bf16) = gelu_erf'(u), out2(bf16) = gelu_erf(u), both from one
+                                  evaluation; u itself is not written.  out2 is required and carries the bits VT_EPI_BF16_GELU
+                                  writes.  The forward of a Linear + GELU whose backward is VT_EPI_BF16_MULAUX              */
+    VT_EPI_BF16_MULAUX = 5 /* out(bf16) = bf16(acc [+ bias]) * aux   (aux bf16 [M,N], e.g. the saved gelu_erf'(u): the
+                              VT_EPI_BF16_DGELU product with gelu' rounded to bf16 once, and no erf / exp per element)       */
 };
 
 typedef struct {
@@ -73,10 +78,10 @@ typedef struct {
     const void* aux; int64_t ldaux;          /* bf16 [M,N]                                    */
     vtRowMap omap;                           /* VT_EPI_F32 only                               */
     int32_t round_bf16;                      /* VT_EPI_F32 only                               */
-    float* colsum_partial;                   /* VT_EPI_BF16_DGELU only, optional: fp32 [ceil(M/192), N]; row t = column
+    float* colsum_partial;                   /* VT_EPI_BF16_DGELU / VT_EPI_BF16_MULAUX only, optional: fp32 [ceil(M/192), N]; row t = column
                                                 sums of the bf16-rounded output over rows [192 t, 192 t + 192) (fixed
                                                 order, no atomics).  vt_sum_slabs over the rows gives the bias gradient
-                                                of the Linear whose pre-activation is `aux`, without re-reading `out` */
+                                                of the Linear whose pre-activation (or its saved gelu') is `aux`, without re-reading `out` */
     float out_scale;                         /* VT_EPI_F32 only: 0 = none; otherwise the finished value (after bias, rounding, residual,
                                                 rowmod) is multiplied by it -- the 1/sqrt(i+1) rescale of the residual stream after
                                                 layer i of models/model_new/base/transformer.py:88-90 -- before out / out2 are written */

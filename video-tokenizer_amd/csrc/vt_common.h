@@ -170,6 +170,13 @@ __device__ __forceinline__ float gelu_erf_grad(float x) {
     gelu_parts(x, cdf, e);
     return fmaf(x * 0.39894228040143267794f, e, cdf);
 }
+// both from ONE gelu_parts evaluation; g / dg carry the bits of gelu_erf(x) / gelu_erf_grad(x)
+__device__ __forceinline__ void gelu_erf_and_grad(float x, float& g, float& dg) {
+    float cdf, e;
+    gelu_parts(x, cdf, e);
+    g = x * cdf;
+    dg = fmaf(x * 0.39894228040143267794f, e, cdf);
+}
 
 // PCG-style integer hash (one round of pcg32's output permutation): the counter-based random numbers of the stochastic
 // codebook search (vt_vq.hip) and of the token gate's Bernoulli draw (vt_stat.hip)

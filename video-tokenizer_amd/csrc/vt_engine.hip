@@ -87,7 +87,7 @@ struct BlockBufs {
     // packed weights
     size_t qkv_wb, qkv_wt, proj_wb, proj_wt, fc1_wb, fc1_wt, fc2_wb, fc2_wt;
     // saved activations
-    size_t x_mid, h1, mean1, rstd1, qkv, lse, o, h2, mean2, rstd2, u, g;
+    size_t x_mid, h1, mean1, rstd1, qkv, lse, o, h2, mean2, rstd2, dgelu, g;   // dgelu = gelu'(fc1 pre-activation), g = its gelu, both bf16
 };
 
 }  // namespace
@@ -195,7 +195,7 @@ static void plan_blocks(const BlockEngine* e, Arena& a, Side& sd, int depth) {
         b.qkv = a.take(Mp * D3 * 2); b.lse = a.take((size_t)e->B * e->H * e->L * 4);
         b.o = a.take(Mp * D * 2);
         b.h2 = a.take(Mp * D * 2); b.mean2 = a.take(Mp * 4); b.rstd2 = a.take(Mp * 4);
-        b.u = a.take(Mp * D4 * 2); b.g = a.take(Mp * D4 * 2);
+        b.dgelu = a.take(Mp * D4 * 2); b.g = a.take(Mp * D4 * 2);
     }
 }
 static void plan_residuals(const BlockEngine* e, Arena& a, Side& sd) {
@@ -459,7 +459,7 @@ static int block_forward(BlockEngine* e, const BlockBufs& b, const vtBlockTensor
     g.bias = w.proj_b; g.residual = x_in; g.ldr = D; g.omap = r.map;
     TRY(vt_gemm_nt(&g, s));
     TRY(vt_layernorm_fwd(WS(float, b.x_mid), r.map, w.norm2_w, w.norm2_b, 1e-5f, r.n, D, WS(void, b.h2), WS(float, b.mean2), WS(float, b.rstd2), s));
-    g = nt(e, ws, WS(void, b.h2), D, WS(void, b.fc1_wb), D, r.n, D4, D, VT_EPI_BF16_GELU, WS(void, b.u), D4);
+    g = nt(e, ws, WS(void, b.h2), D, WS(void, b.fc1_wb), D, r.n, D4, D, VT_EPI_BF16_GELU_GRAD, WS(void, b.dgelu), D4);
     g.out2 = WS(void, b.g); g.ldo2 = D4; g.bias = w.fc1_b;
     TRY(vt_gemm_nt(&g, s));
     g = nt(e, ws, WS(void, b.g), D4, WS(void, b.fc2_wb), D4, r.n, D, D4, VT_EPI_F32, x_out, D);
@@ -701,9 +701,9 @@ static int block_backward(BlockEngine* e, const BlockBufs& b, const vtBlockTenso
     void* du = WS(void, kept ? kept->du : g0.du);
     void* dqkv = WS(void, g0.dqkv);
     if (kept) TRY(vt_cast_rows(dX, r.map, r.n, D, dXa, D, s));
-    // fc2 dgrad fused with GELU': du = (dx_out . W2) * gelu'(u)
-    vtGemmNT g = nt(e, ws, dXa, D, WS(void, b.fc2_wt), D, r.n, D4, D, VT_EPI_BF16_DGELU, du, D4);
-    g.aux = WS(void, b.u); g.ldaux = D4;
+    // fc2 dgrad fused with GELU': du = (dx_out . W2) * gelu'(u), gelu'(u) as the fc1 forward saved it (bf16)
+    vtGemmNT g = nt(e, ws, dXa, D, WS(void, b.fc2_wt), D, r.n, D4, D, VT_EPI_BF16_MULAUX, du, D4);
+    g.aux = WS(void, b.dgelu); g.ldaux = D4;
     g.colsum_partial = WS(float, g0.cs_part);  // fc1 bias gradient = column sums of du, taken in the epilogue; summed at the flush
     TRY(vt_gemm_nt(&g, s));
     queue_slab_sum(e, WS(float, g0.cs_part), (r.n + 191) / 192, D4, gr.fc1_b);

@@ -296,6 +296,13 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(const NTArgs a) {
                     st_stream((bf16x4*)o, h);
                     st_stream((bf16x4*)((bf16_t*)p.out2 + (int64_t)m * p.ldo2 + n),
                               (bf16x4){f2bf(gelu_erf(bf2f(h[0]))), f2bf(gelu_erf(bf2f(h[1]))), f2bf(gelu_erf(bf2f(h[2]))), f2bf(gelu_erf(bf2f(h[3])))});
+                } else if constexpr (EPI == VT_EPI_BF16_GELU_GRAD) {
+                    bf16x4 g, dg;
+                    gelu_and_grad4(h, g, dg);
+                    st_stream((bf16x4*)o, dg);
+                    st_stream((bf16x4*)((bf16_t*)p.out2 + (int64_t)m * p.ldo2 + n), g);
+                } else if constexpr (EPI == VT_EPI_BF16_MULAUX) {
+                    st_stream((bf16x4*)o, mul_aux4(h, ld_stream((const bf16x4*)((const bf16_t*)p.aux + (int64_t)m * p.ldaux + n))));
                 } else {
                     const bf16x4 uu = ld_stream((const bf16x4*)((const bf16_t*)p.aux + (int64_t)m * p.ldaux + n));
                     st_stream((bf16x4*)o, (bf16x4){f2bf(bf2f(h[0]) * gelu_erf_grad(bf2f(uu[0]))), f2bf(bf2f(h[1]) * gelu_erf_grad(bf2f(uu[1]))),
@@ -569,10 +576,12 @@ extern "C" int vt_gemm_nt(const vtGemmNT* ph, vtStream stream) {
                  "vt_gemm_nt: out/bias/residual/rowmod must be 16-byte aligned (out2/aux 8-byte)");
     VT_CHECK_ARG(!p.rowmod || p.N % 4 == 0, "vt_gemm_nt: rowmod needs N %% 4 == 0");
     if (p.epi == VT_EPI_BF16_GELU) VT_CHECK_ARG(p.out2 && p.ldo2 % 4 == 0, "vt_gemm_nt: GELU epilogue needs out2");
+    if (p.epi == VT_EPI_BF16_GELU_GRAD) VT_CHECK_ARG(p.out2 && p.ldo2 % 4 == 0, "vt_gemm_nt: GELU_GRAD epilogue needs out2");
     if (p.epi == VT_EPI_BF16_DGELU) VT_CHECK_ARG(p.aux && p.ldaux % 4 == 0, "vt_gemm_nt: DGELU epilogue needs aux");
+    if (p.epi == VT_EPI_BF16_MULAUX) VT_CHECK_ARG(p.aux && p.ldaux % 4 == 0, "vt_gemm_nt: MULAUX epilogue needs aux");
     VT_CHECK_ARG(p.out_scale == 0.f || p.epi == VT_EPI_F32, "vt_gemm_nt: out_scale only with VT_EPI_F32");
-    VT_CHECK_ARG(!p.colsum_partial || (p.epi == VT_EPI_BF16_DGELU && p.N % 4 == 0),
-                 "vt_gemm_nt: colsum_partial needs the DGELU epilogue and N %% 4 == 0 (it always runs on the 192-row tile kernel)");
+    VT_CHECK_ARG(!p.colsum_partial || ((p.epi == VT_EPI_BF16_DGELU || p.epi == VT_EPI_BF16_MULAUX) && p.N % 4 == 0),
+                 "vt_gemm_nt: colsum_partial needs the DGELU or MULAUX epilogue and N %% 4 == 0 (it always runs on the 192-row tile kernel)");
     if (p.epi == VT_EPI_F32) {
         VT_CHECK_ARG(!p.residual || p.ldr % 4 == 0, "vt_gemm_nt: ldr must be a multiple of 4");
         VT_CHECK_ARG(!p.rowmod || p.rowmod_period > 0, "vt_gemm_nt: rowmod needs a period");
@@ -654,7 +663,7 @@ extern "C" int vt_gemm_nt(const vtGemmNT* ph, vtStream stream) {
         constexpr int LDS4 = 4 * 2 * TILE_B;
         if (!attr_set) {
             hipError_t e = hipSuccess;
-            for (int epi : {VT_EPI_BF16, VT_EPI_BF16_GELU, VT_EPI_F32, VT_EPI_BF16_DGELU})
+            for (int epi : VT_EPI_ALL)
                 dispatch_epi(epi, [&](auto k) {
                     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gemm_nt_kernel<decltype(k)::value, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS4);
                     return 0;

@@ -61,22 +61,28 @@ struct NTGeo {
 };
 
 // gelu(u) of the fc1 epilogue by table.  It is applied to a value that is ALREADY bf16 (the rounded pre-activation u), so it is
-// a function of 16 bits: the 10 KiB of LDS above the 144-KiB ring hold bf16 gelu(u) for |u| in [2^-16, 16), both signs
-// (2 x 20 x 128 entries), filled once per workgroup at kernel start by gelu_erf itself -- every entry is bit-for-bit what the
-// arithmetic returns.  A wave whose 4-column group holds a value outside the range (~1e-5 of the elements) takes the arithmetic
-// for that group (wave-uniform branch), so the output is bit-identical to the arithmetic everywhere (the 128x128 kernel keeps the
-// arithmetic; tests compare the two with torch.equal).  Measured gain: 84.9 -> 82.2 us on fc1 forward at the step's shape
-// (tools/gemm_gelu_epilogue.py) -- small, because the GELU epilogue's extra 17 us over the plain one is mostly its second 75-MB
-// output, written by all 256 CUs in phase, not its ~17 VALU + v_rcp + v_exp per element.  The same table for gelu' (fp32, 16 KiB)
-// was built for the fc2-dgrad epilogue and dropped: that instantiation has no register to spare (256 allocated) and spilled
-// around the main loop.
+// a function of 16 bits: the LDS above the 144-KiB ring holds it for a range of |u|, both signs, filled once per workgroup at kernel
+// start by the arithmetic itself -- every entry is bit-for-bit what the arithmetic returns.  A wave whose column group holds a value
+// outside the range takes the arithmetic for that group (wave-uniform branch), so the output is bit-identical to the arithmetic
+// everywhere (the 128x128 kernel keeps the arithmetic; tests compare the two with torch.equal).
+//   VT_EPI_BF16_GELU:      bf16 gelu(u), |u| in [2^-16, 16): 2 x 20 x 128 entries = 10 KiB.  Measured gain: 84.9 -> 82.2 us on fc1 forward
+//                          at the step's shape (tools/gemm_gelu_epilogue.py) -- small, because the GELU epilogue's extra 17 us over
+//                          the plain one is mostly its second 75-MB output, written by all 256 CUs in phase, not its arithmetic.
+//   VT_EPI_BF16_GELU_GRAD: (gelu(u), gelu'(u)) pairs, 4 bytes, |u| in [2^-12, 16): 2 x 16 x 128 entries = 16 KiB, all that is left of the
+//                          160 KiB.  This is where the step's gelu' is evaluated now: the fc2-dgrad epilogue (VT_EPI_BF16_MULAUX) only
+//                          multiplies by the saved bf16 value.  Against both by arithmetic (79.2 us) and gelu by the 10-KiB table with
+//                          gelu' by arithmetic (88.2 us: the table's wave-uniform test AND a full evaluation) the pair table runs at
+//                          76.7 us, VT_EPI_BF16_GELU's own time (profiles/gelu_grad_saved_in_fc1_forward_ab.log).
+// An fp32 gelu' table (16 KiB) inside the fc2-dgrad epilogue itself (VT_EPI_BF16_DGELU) was built in round 5 and dropped: that
+// instantiation has no register to spare (255 allocated) and spilled around the main loop.  VT_EPI_BF16_MULAUX needs 224.
 template <int EPI>
 struct GeluTab {
-    static constexpr bool ON = EPI == VT_EPI_BF16_GELU;
-    static constexpr int LO_EXP = 127 - 16;
-    static constexpr int NEXP = 20;
+    static constexpr bool PAIR = EPI == VT_EPI_BF16_GELU_GRAD;   // entries are (gelu, gelu') pairs: 16 exponents of 4-byte entries fill the 16 KiB behind the ring
+    static constexpr bool ON = EPI == VT_EPI_BF16_GELU || PAIR;
+    static constexpr int LO_EXP = PAIR ? 127 - 12 : 127 - 16;
+    static constexpr int NEXP = PAIR ? 16 : 20;
     static constexpr int PER_SIGN = NEXP * 128;
-    static constexpr int ENTRY = 2;
+    static constexpr int ENTRY = PAIR ? 4 : 2;
     static constexpr int BYTES = ON ? 2 * PER_SIGN * ENTRY : 0;
     // entry index of the bf16 bit pattern `b`, or >= 2 * PER_SIGN when out of range
     static __device__ __forceinline__ unsigned index(unsigned b) {
@@ -106,6 +112,31 @@ __device__ __forceinline__ bf16xN<N> gelu_lookup(const bf16xN<N>& h, const bf16_
 #pragma unroll
     for (int e = 0; e < N; ++e) gl[e] = f2bf(gelu_erf(bf2f(h[e])));
     return gl;
+}
+// gelu (g) and gelu' (dg) of the N bf16 values a lane read back, for VT_EPI_BF16_GELU_GRAD: one 4-byte table entry per value, or one
+// gelu_parts evaluation per value for the whole wave when some lane is outside the table (the same bits either way)
+template <int N, bool TABLE>
+__device__ __forceinline__ void gelu_grad_lookup(const bf16xN<N>& h, const char* tab, bf16xN<N>& g, bf16xN<N>& dg) {
+    using GT = GeluTab<VT_EPI_BF16_GELU_GRAD>;
+    if constexpr (TABLE) {
+        unsigned idx[N], any = 0;
+#pragma unroll
+        for (int e = 0; e < N; ++e) { idx[e] = GT::index(bf16_bits(h[e])); any |= idx[e]; }
+        if (__builtin_amdgcn_ballot_w64((any & 0x8000u) != 0) == 0) {
+#pragma unroll
+            for (int e = 0; e < N; ++e) {
+                const unsigned w = ((const unsigned*)tab)[idx[e]];
+                g[e] = bf16_from_bits(w & 0xFFFFu), dg[e] = bf16_from_bits(w >> 16);
+            }
+            return;
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < N; ++e) {
+        float gf, df;
+        gelu_erf_and_grad(bf2f(h[e]), gf, df);
+        g[e] = f2bf(gf), dg[e] = f2bf(df);
+    }
 }
 
 // The P 16-B-per-lane DMA pieces of a K-tile (pieces 0..PA-1 = A rows, PA..P-1 = B rows).  A lane's byte offset inside
@@ -264,7 +295,13 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm_nt192_kernel(const NT192Args
         for (int e = tid; e < 2 * GT::PER_SIGN; e += G::THREADS) {
             const unsigned sgn = e >= GT::PER_SIGN ? 1u : 0u;
             const float x = bf2f(bf16_from_bits((sgn << 15) | (unsigned)(e - (int)sgn * GT::PER_SIGN + (GT::LO_EXP << 7))));
-            ((bf16_t*)tab)[e] = f2bf(gelu_erf(x));
+            if constexpr (GT::PAIR) {
+                float gf, df;
+                gelu_erf_and_grad(x, gf, df);
+                ((unsigned*)tab)[e] = bf16_bits(f2bf(gf)) | (bf16_bits(f2bf(df)) << 16);
+            } else {
+                ((bf16_t*)tab)[e] = f2bf(gelu_erf(x));
+            }
         }
     }
     constexpr bool PERSIST = WN == 4;   // the 192x96 experiment stays one tile per workgroup
@@ -346,6 +383,8 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm_nt192_kernel(const NT192Args
         if ((p.N & 3) == 0) {
             // the epilogue's per-thread coordinates are recomputed per output tile: hoisted out of the persistent loop they would
             // sit in registers across the main loop, which has none to spare (256 allocated, spill-free)
+            constexpr bool GG = EPI == VT_EPI_BF16_GELU_GRAD;                             // out = gelu'(u), out2 = gelu(u)
+            constexpr bool MUL = EPI == VT_EPI_BF16_DGELU || EPI == VT_EPI_BF16_MULAUX;   // out = h * f(aux), with column sums
             int tid_e = tid;
             if constexpr (EPI != VT_EPI_BF16_DGELU) asm volatile("" : "+v"(tid_e));   // (the gelu' instantiation sits at 256 registers and spills WITH it)
             const int fr_e = tid_e & 15, fq_e = (tid_e & 63) >> 4;
@@ -357,11 +396,11 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm_nt192_kernel(const NT192Args
             // bf16-rounded value (autocast order).
             constexpr int UPR = G::TNW / 4;             // 8-B units per tile row
             constexpr int STRIDE = G::TNW * 2 + 8;      // bytes
-            constexpr int RL = G::THREADS / UPR;        // gelu' path: row lanes (10); RL * UPR of the threads are active
+            constexpr int RL = G::THREADS / UPR;        // gelu' / aux path: row lanes (10); RL * UPR of the threads are active
             constexpr int NIT = (TM + RL - 1) / RL;
             [[maybe_unused]] bf16x4 uu_pre[NIT];
-            if constexpr (EPI == VT_EPI_BF16_DGELU) {
-                // the pre-activations this thread will need after the read-back: all NIT loads go out now, so their HBM
+            if constexpr (MUL) {
+                // the `aux` values this thread will need after the read-back: all NIT loads go out now, so their HBM
                 // latency runs under the staging writes and the barrier instead of 20 times in the store loop
                 const int c = tid_e % UPR, rl = tid_e / UPR;
                 const int n = en0 + c * 4;
@@ -387,10 +426,12 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm_nt192_kernel(const NT192Args
                     *(bf16x4*)(smem + (wm * 96 + i * 16 + fr_e) * STRIDE + (wn * 12 + j * 4 + fq_e) * 8) = (bf16x4){f2bf(v[0]), f2bf(v[1]), f2bf(v[2]), f2bf(v[3])};
                 }
             __syncthreads();
-            if constexpr (EPI == VT_EPI_BF16_DGELU) {
+            if constexpr (MUL) {
                 // a thread keeps ONE 4-column group and walks the rows (48 lanes cover a 384-B row, the rest of the wave the
                 // next row), so the column sums of the rounded output -- the bias gradient of the Linear whose
-                // pre-activation is `aux` -- fall out of the epilogue instead of a separate pass over M x N
+                // pre-activation is behind `aux` -- fall out of the epilogue instead of a separate pass over M x N.
+                // (MULAUX is bound by its memory instructions, yet 8 columns and 16 bytes per thread measured the same:
+                // profiles/gelu_grad_saved_in_fc1_forward_ab.log)
                 const int c = tid_e % UPR, rl = tid_e / UPR;
                 const int n = en0 + c * 4;
                 f32x4 cs = {0.f, 0.f, 0.f, 0.f};
@@ -402,7 +443,9 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm_nt192_kernel(const NT192Args
                         if (row < TM && m < p.M) {
                             const bf16x4 h = *(const bf16x4*)(smem + row * STRIDE + c * 8);
                             const bf16x4 uu = uu_pre[it];
-                            const bf16x4 r = {f2bf(bf2f(h[0]) * gelu_erf_grad(bf2f(uu[0]))), f2bf(bf2f(h[1]) * gelu_erf_grad(bf2f(uu[1]))),
+                            bf16x4 r;
+                            if constexpr (EPI == VT_EPI_BF16_MULAUX) r = mul_aux4(h, uu);
+                            else r = (bf16x4){f2bf(bf2f(h[0]) * gelu_erf_grad(bf2f(uu[0]))), f2bf(bf2f(h[1]) * gelu_erf_grad(bf2f(uu[1]))),
                                               f2bf(bf2f(h[2]) * gelu_erf_grad(bf2f(uu[2]))), f2bf(bf2f(h[3]) * gelu_erf_grad(bf2f(uu[3])))};
                             st_stream_any((bf16x4*)((bf16_t*)p.out + (int64_t)m * p.ldo + n), r);
                             cs += (f32x4){bf2f(r[0]), bf2f(r[1]), bf2f(r[2]), bf2f(r[3])};
@@ -425,7 +468,7 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm_nt192_kernel(const NT192Args
             // Round 4: 16 bytes per lane on the way out (two 8-byte image reads, ONE global_store_dwordx4: a wave instruction writes 1 KiB).
             // 8-byte accesses run at 0.54-0.70 of the 16-byte rate (MI355X_MICROARCH, visibility table) and the epilogue is what a round
             // of this kernel pays outside its main loop (6-13 us, all 256 CUs storing at once).  Needs 8-column alignment of the output.
-            if ((p.N & 7) == 0 && (p.ldo & 7) == 0 && (EPI != VT_EPI_BF16_GELU || (p.ldo2 & 7) == 0)) {
+            if ((p.N & 7) == 0 && (p.ldo & 7) == 0 && ((EPI != VT_EPI_BF16_GELU && !GG) || (p.ldo2 & 7) == 0)) {
                 constexpr int UPR16 = G::TNW / 8;                        // 16-B units per tile row
                 constexpr int NIT16 = TM * UPR16 / G::THREADS, RB16 = 3;
                 static_assert(NIT16 % RB16 == 0, "read-back batches");
@@ -447,6 +490,13 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm_nt192_kernel(const NT192Args
                         const int m = em0 + piece_row(it0 + u), n = en0 + piece_col(it0 + u);
                         if (m >= p.M || n >= p.N) continue;
                         const bf16x8 h = hh[u];
+                        if constexpr (GG) {
+                            bf16x8 g, dg;
+                            gelu_grad_lookup<8, TABLE>(h, tab, g, dg);
+                            st_stream_any((bf16x8*)((bf16_t*)p.out + (int64_t)m * p.ldo + n), dg);
+                            st_stream_any((bf16x8*)((bf16_t*)p.out2 + (int64_t)m * p.ldo2 + n), g);
+                            continue;
+                        }
                         st_stream_any((bf16x8*)((bf16_t*)p.out + (int64_t)m * p.ldo + n), h);
                         if constexpr (EPI == VT_EPI_BF16_GELU) {
                             st_stream_any((bf16x8*)((bf16_t*)p.out2 + (int64_t)m * p.ldo2 + n), gelu_lookup<8, TABLE>(h, (const bf16_t*)tab));
@@ -476,6 +526,13 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm_nt192_kernel(const NT192Args
                     if (m >= p.M || n >= p.N) continue;
                     const bf16x4 h = hh[u];
                     bf16_t* o = (bf16_t*)p.out + (int64_t)m * p.ldo + n;
+                    if constexpr (GG) {
+                        bf16x4 g, dg;
+                        gelu_grad_lookup<4, TABLE>(h, tab, g, dg);
+                        st_stream_any((bf16x4*)o, dg);
+                        st_stream_any((bf16x4*)((bf16_t*)p.out2 + (int64_t)m * p.ldo2 + n), g);
+                        continue;
+                    }
                     st_stream_any((bf16x4*)o, h);
                     if constexpr (EPI == VT_EPI_BF16_GELU) {
                         st_stream_any((bf16x4*)((bf16_t*)p.out2 + (int64_t)m * p.ldo2 + n), gelu_lookup<4, TABLE>(h, (const bf16_t*)tab));
@@ -997,7 +1054,7 @@ int vt_gemm192_init() {
     auto allow = [&](const void* kernel, int bytes) {
         if (e == hipSuccess) e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     };
-    for (int epi : {VT_EPI_BF16, VT_EPI_BF16_GELU, VT_EPI_F32, VT_EPI_BF16_DGELU})
+    for (int epi : VT_EPI_ALL)
         dispatch_epi(epi, [&](auto k) {
             constexpr int EPI = decltype(k)::value;
             allow((const void*)gemm_nt192_kernel<EPI, 4>, nt192_lds_bytes<EPI, 4>());

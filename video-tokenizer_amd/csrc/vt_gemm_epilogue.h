@@ -7,6 +7,23 @@
 
 #include "vt_common.h"
 
+// every epilogue code, for the loops that prepare each kernel instantiation
+constexpr int VT_EPI_ALL[] = {VT_EPI_BF16, VT_EPI_BF16_GELU, VT_EPI_F32, VT_EPI_BF16_DGELU, VT_EPI_BF16_GELU_GRAD, VT_EPI_BF16_MULAUX};
+
+// gelu'(u) and gelu(u) of four bf16 pre-activations, each pair from one gelu_parts evaluation (VT_EPI_BF16_GELU_GRAD)
+__device__ __forceinline__ void gelu_and_grad4(const bf16x4& u, bf16x4& g, bf16x4& dg) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        float gf, df;
+        gelu_erf_and_grad(bf2f(u[e]), gf, df);
+        g[e] = f2bf(gf), dg[e] = f2bf(df);
+    }
+}
+// bf16(h * aux) of four bf16 pairs (VT_EPI_BF16_MULAUX); the fp32 product of two bf16 values is exact
+__device__ __forceinline__ bf16x4 mul_aux4(const bf16x4& h, const bf16x4& a) {
+    return (bf16x4){f2bf(bf2f(h[0]) * bf2f(a[0])), f2bf(bf2f(h[1]) * bf2f(a[1])), f2bf(bf2f(h[2]) * bf2f(a[2])), f2bf(bf2f(h[3]) * bf2f(a[3]))};
+}
+
 // Calls f with the run-time epilogue `epi` as a compile-time constant (std::integral_constant<int, VT_EPI_*>) and returns what it returns.
 template <typename F>
 static inline int dispatch_epi(int epi, F&& f) {
@@ -15,6 +32,8 @@ static inline int dispatch_epi(int epi, F&& f) {
         case VT_EPI_BF16_GELU: return f(std::integral_constant<int, VT_EPI_BF16_GELU>{});
         case VT_EPI_F32: return f(std::integral_constant<int, VT_EPI_F32>{});
         case VT_EPI_BF16_DGELU: return f(std::integral_constant<int, VT_EPI_BF16_DGELU>{});
+        case VT_EPI_BF16_GELU_GRAD: return f(std::integral_constant<int, VT_EPI_BF16_GELU_GRAD>{});
+        case VT_EPI_BF16_MULAUX: return f(std::integral_constant<int, VT_EPI_BF16_MULAUX>{});
         default: vt_set_error("vt_gemm_nt: unknown epilogue %d", epi); return VT_ERR_INVALID;
     }
 }
@@ -38,6 +57,14 @@ __device__ __forceinline__ void nt_epilogue(const vtGemmNT& p, const RowMap& oma
             *(bf16x4*)((bf16_t*)p.out + orow * p.ldo + n) =
                 (bf16x4){f2bf(v[0] * gelu_erf_grad(bf2f(uu[0]))), f2bf(v[1] * gelu_erf_grad(bf2f(uu[1]))),
                          f2bf(v[2] * gelu_erf_grad(bf2f(uu[2]))), f2bf(v[3] * gelu_erf_grad(bf2f(uu[3])))};
+        } else if constexpr (EPI == VT_EPI_BF16_GELU_GRAD) {
+            bf16x4 g, dg;
+            gelu_and_grad4((bf16x4){f2bf(v[0]), f2bf(v[1]), f2bf(v[2]), f2bf(v[3])}, g, dg);
+            *(bf16x4*)((bf16_t*)p.out + orow * p.ldo + n) = dg;
+            *(bf16x4*)((bf16_t*)p.out2 + orow * p.ldo2 + n) = g;
+        } else if constexpr (EPI == VT_EPI_BF16_MULAUX) {
+            *(bf16x4*)((bf16_t*)p.out + orow * p.ldo + n) =
+                mul_aux4((bf16x4){f2bf(v[0]), f2bf(v[1]), f2bf(v[2]), f2bf(v[3])}, *(const bf16x4*)((const bf16_t*)p.aux + (int64_t)m * p.ldaux + n));
         } else {  // VT_EPI_F32
             if (p.round_bf16) v = (f32x4){round_bf16(v[0]), round_bf16(v[1]), round_bf16(v[2]), round_bf16(v[3])};
             if (p.residual) v += *(const f32x4*)(p.residual + orow * p.ldr + n);   // (a streaming load of these 64-B line halves fetches every line twice)
@@ -60,6 +87,13 @@ __device__ __forceinline__ void nt_epilogue(const vtGemmNT& p, const RowMap& oma
         } else if constexpr (EPI == VT_EPI_BF16_DGELU) {
             const float u = bf2f(((const bf16_t*)p.aux)[(int64_t)m * p.ldaux + n + r]);
             ((bf16_t*)p.out)[orow * p.ldo + n + r] = f2bf(v * gelu_erf_grad(u));
+        } else if constexpr (EPI == VT_EPI_BF16_GELU_GRAD) {
+            float gf, df;
+            gelu_erf_and_grad(bf2f(f2bf(v)), gf, df);
+            ((bf16_t*)p.out)[orow * p.ldo + n + r] = f2bf(df);
+            ((bf16_t*)p.out2)[orow * p.ldo2 + n + r] = f2bf(gf);
+        } else if constexpr (EPI == VT_EPI_BF16_MULAUX) {
+            ((bf16_t*)p.out)[orow * p.ldo + n + r] = f2bf(bf2f(f2bf(v)) * bf2f(((const bf16_t*)p.aux)[(int64_t)m * p.ldaux + n + r]));
         } else {
             if (p.round_bf16) v = round_bf16(v);
             if (p.residual) v += p.residual[orow * p.ldr + n + r];

@@ -12,7 +12,7 @@ _lib = None
 
 c_i32, c_i64, c_f32, c_u64, c_vp, c_sz = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_size_t
 
-EPI_BF16, EPI_BF16_GELU, EPI_F32, EPI_BF16_DGELU = 0, 1, 2, 3
+EPI_BF16, EPI_BF16_GELU, EPI_F32, EPI_BF16_DGELU, EPI_BF16_GELU_GRAD, EPI_BF16_MULAUX = 0, 1, 2, 3, 4, 5
 TN_MAX_GROUP = 16
 
 
@@ -284,7 +284,7 @@ def gemm_nt(A, B, epi=EPI_BF16, bias=None, out=None, out2=None, residual=None, r
     if out is None:
         rows = out_rows if out_rows is not None else M
         out = torch.empty(rows, N, device=dev, dtype=torch.float32 if epi == EPI_F32 else torch.bfloat16)
-    if epi == EPI_BF16_GELU and out2 is None:
+    if epi in (EPI_BF16_GELU, EPI_BF16_GELU_GRAD) and out2 is None:
         out2 = torch.empty(M, N, device=dev, dtype=torch.bfloat16)
     p = GemmNT()
     p.A, p.lda, p.B, p.ldb = A.data_ptr(), A.stride(0), B.data_ptr(), B.stride(0)
@@ -306,7 +306,7 @@ def gemm_nt(A, B, epi=EPI_BF16, bias=None, out=None, out2=None, residual=None, r
     else:
         p.splitk_ws, p.splitk_ws_bytes, p.splitk = None, 0, 1
     check(lib().vt_gemm_nt(ctypes.byref(p), stream()), "vt_gemm_nt")
-    return (out, out2) if epi == EPI_BF16_GELU else out
+    return (out, out2) if epi in (EPI_BF16_GELU, EPI_BF16_GELU_GRAD) else out
 
 
 def gemm_tn_grouped(problems):
