@@ -217,6 +217,20 @@ int vt_attention_fwd_rows(const void* qkv, int32_t B, int32_t L, int32_t H, int3
                           vtStream stream);
 int vt_attention_bwd_rows(const void* qkv, const void* o_compact, const void* dO_compact, const float* lse2, int32_t B, int32_t L,
                           int32_t H, int32_t hd, int32_t q_begin, void* dqkv, float* delta_ws, vtStream stream);
+/* Cross attention: the queries come from one tensor, the keys and values from another (CrossAttention of
+ * models/model_design/base/transformer.py:92-141, `flash_attn_func(q, k, v)` with 2048 queries and 256 first-frame keys).  All
+ * operands bf16.  Row r of batch b of q starts at q + (b * Lq + r) * q_rs, head h at columns 64h .. 64h+63 of the row; k and v
+ * likewise with Lk rows per batch and strides of their own (two pointers: k may be a normalised copy while v is read in place from
+ * the to_kv output).  o / dO compact [B, Lq, H, 64]; lse2, delta_ws fp32 [B, H, Lq].  dq covers B * Lq rows, dk and dv B * Lk
+ * rows; columns 0 .. 64H-1 of every row are written, the rest of a wider buffer is not touched.  Scale 64^-0.5, no mask, any
+ * Lq >= 1 and Lk >= 1.  hd must be 64, every stride >= 64H, below 2^24 and a multiple of 8 elements, every pointer 16-byte aligned
+ * (VT_ERR_INVALID + vt_last_error otherwise).  The kernels and tile code of vt_attention_*: with q = qkv, k = qkv + 64H,
+ * v = qkv + 128H, every stride 192H and Lq = Lk the results are bit-identical to vt_attention_fwd / _bwd. */
+int vt_attention_cross_fwd(const void* q, int64_t q_rs, const void* k, int64_t k_rs, const void* v, int64_t v_rs, int32_t B, int32_t Lq,
+                           int32_t Lk, int32_t H, int32_t hd, void* o, float* lse2, vtStream stream);
+int vt_attention_cross_bwd(const void* q, int64_t q_rs, const void* k, int64_t k_rs, const void* v, int64_t v_rs, const void* o,
+                           const void* dO, const float* lse2, int32_t B, int32_t Lq, int32_t Lk, int32_t H, int32_t hd, void* dq,
+                           int64_t dq_rs, void* dk, int64_t dk_rs, void* dv, int64_t dv_rs, float* delta_ws, vtStream stream);
 
 /* ------------------------------------------------------------------------------------------
  * Vector quantisation (SimpleVectorQuantizer.forward, models/bottleneck.py:262-324).
@@ -349,6 +363,12 @@ int vt_qknorm_rope_bwd(const void* qkvg, const void* dqkv, int64_t M, int32_t L,
                        float* dk_b, void* workspace, vtStream stream);
 int vt_sigmoid_gate_fwd(const void* o, const void* qkvg, int64_t M, int32_t D, void* og, vtStream stream);
 int vt_sigmoid_gate_bwd(const void* dog, const void* o, const void* qkvg, int64_t M, int32_t D, void* d_o, void* dqkvg, vtStream stream);
+/* the same pair with the gate at any column offset and row stride (gate / dgate point at the first gate column of row 0; strides
+ * >= D, multiples of 8): CrossAttention of model_design reads it from columns D..2D of the [M, 2D] projection [to_q ; to_gate].
+ * gate = qkvg + 3D with stride 4D is vt_sigmoid_gate_*, bit for bit. */
+int vt_sigmoid_gate_cols_fwd(const void* o, const void* gate, int64_t gate_rs, int64_t M, int32_t D, void* og, vtStream stream);
+int vt_sigmoid_gate_cols_bwd(const void* dog, const void* o, const void* gate, int64_t gate_rs, int64_t M, int32_t D, void* d_o, void* dgate,
+                             int64_t dgate_rs, vtStream stream);
 int vt_geglu_fwd(const void* h, int64_t M, int32_t I, void* a, int64_t lda, vtStream stream);
 int vt_geglu_bwd(const void* da, int64_t lda, const void* h, int64_t M, int32_t I, void* dh, vtStream stream);
 /* dst[r, :] = scale * src[r, :] (fp32, may be in place) and/or its bf16 copy: the incoming gradient of a layer whose output was
@@ -373,6 +393,22 @@ int vt_rmsnorm_fwd(const float* x, const float* w, float eps, int64_t rows, int3
 size_t vt_rmsnorm_bwd_workspace_bytes(int32_t dim);
 int vt_rmsnorm_bwd(const void* dy_bf16, const float* x, const float* w, const float* rstd, const float* dres, int64_t rows, int32_t dim,
                    float* dx, void* dx_bf16, float* dw, void* workspace, vtStream stream);
+/* vt_rmsnorm_any_*: the same kernels, additionally at the widths 128, 256 and 512 of model_design (its 'small' is 512 wide, which
+ * vt_rmsnorm_* refuses); bit-equal to vt_rmsnorm_* at the widths both accept. */
+int vt_rmsnorm_any_fwd(const float* x, const float* w, float eps, int64_t rows, int32_t dim, void* y_bf16, float* rstd, vtStream stream);
+size_t vt_rmsnorm_any_bwd_workspace_bytes(int32_t dim);
+int vt_rmsnorm_any_bwd(const void* dy_bf16, const float* x, const float* w, const float* rstd, const float* dres, int64_t rows, int32_t dim,
+                       float* dx, void* dx_bf16, float* dw, void* workspace, vtStream stream);
+/* RMSNorm over each 64-element head vector of a bf16 row: q_norm / k_norm of model_design's attention layers
+ * (models/model_design/base/transformer.py:18-27, 114-115, 134-135).  x, y, dy, dx bf16 [M, >= 64H] with a row stride each (>= 64H, a
+ * multiple of 8; 16-byte aligned), w / dw fp32 [64].  Rounding of the reference under autocast: y = bf16(bf16(x * rstd) * w),
+ * rstd = rsqrt(mean(x^2) + eps) in fp32.  Not in place (the backward reads x).  Backward: rstd recomputed,
+ * dx = rstd g - x rstd^3 / 64 sum(x g), g = w dy; dx may be dy itself (same pointer and stride) and otherwise overlaps neither dy nor x; dw = sum dy x rstd from 512 per-workgroup partials in `workspace`
+ * (vt_head_rmsnorm_bwd_workspace_bytes()) summed in a fixed order by a second launch: no float atomics, bit-identical run to run. */
+int vt_head_rmsnorm_fwd(const void* x, int64_t x_rs, const float* w, float eps, int64_t M, int32_t H, void* y, int64_t y_rs, vtStream stream);
+size_t vt_head_rmsnorm_bwd_workspace_bytes(void);
+int vt_head_rmsnorm_bwd(const void* dy, int64_t dy_rs, const void* x, int64_t x_rs, const float* w, float eps, int64_t M, int32_t H, void* dx,
+                        int64_t dx_rs, float* dw, void* workspace, vtStream stream);
 int vt_swiglu_fwd(const void* h, int64_t M, int32_t I, void* a, vtStream stream);
 int vt_swiglu_bwd(const void* da, const void* h, int64_t M, int32_t I, void* dh, vtStream stream);
 int vt_decode_attention(const void* q, const void* k_cache, const void* v_cache, int32_t B, int32_t H, int64_t Lmax, int32_t n_keys, void* o,

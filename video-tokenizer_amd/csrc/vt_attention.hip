@@ -4,6 +4,10 @@
 //
 // Layouts: qkv bf16 [B, L, 3, H, 64] (the qkv Linear's output, reshape (B,N,3,H,hd)); o / dO bf16
 // [B, L, H, 64]; lse2 fp32 [B, H, L] = log2-domain log-sum-exp of the scaled scores; delta fp32 [B,H,L].
+// CROSS instantiations (vt_attention_cross_*; CrossAttention of models/model_design/base/transformer.py:92-141): q, k and v are
+// three pointers with a row stride each, Lq query rows and Lk key rows per batch; o / dO [B, Lq, H, 64], lse2 / delta [B, H, Lq].
+// The same kernels and tile code: a packed launch is the special case q = qkv, k = q + D, v = k + D, every stride 3D, Lq = Lk,
+// which the packed instantiations know at compile time (one stride register, one set of staging offsets) and CROSS ones do not.
 //
 // Common skeleton (one workgroup = 4 waves, each wave owns 32 "stationary" rows held in registers as
 // MFMA B operands; 64-row "streaming" tiles are staged global -> LDS with 16-B global_load_lds,
@@ -34,40 +38,81 @@ namespace {
 // One workgroup's (batch, head, row-block) and the first Q / K / V row of that head.  1-D grid, XCD-aware: the nblk row-blocks of one
 // (batch, head) get consecutive ids inside ONE XCD's chunk, so the tiles they all stream (K/V in fwd and dQ, Q/dO in dK/dV) are
 // fetched into that XCD's L2 once instead of once per XCD.  Returned BY VALUE: the fields are scalars the kernels keep in SGPRs.
+// The operands of a launch (kernel arguments).  Packed: q = qkv [B, L, 3, H, HD] and Lq = L are read, the other fields are not.
+struct AttnOps {
+    const bf16_t *q, *k, *v;
+    int64_t q_rs, k_rs, v_rs;        // row strides (elements)
+    int Lq, Lk;                      // rows per batch of q and of k / v
+};
+// Where the gradients go.  Packed: dq = dqkv, laid out as qkv.
+struct AttnGrads {
+    bf16_t *dq, *dk, *dv;
+    int64_t dq_rs, dk_rs, dv_rs;
+};
 struct HeadPtrs {
     int b, h, blk;
-    int64_t rs, ors;                 // row strides (elements) of qkv [B, L, 3, H, HD] and of o / dO [B, Lq, H, HD]
+    int Lq, Lk;
+    int64_t q_rs, k_rs, v_rs, ors;   // row strides (elements) of q, k, v and of o / dO [B, Lq, H, HD]
     const bf16_t *qb, *kb, *vb;
 };
-template <int HD>
-__device__ __forceinline__ HeadPtrs head_ptrs(const bf16_t* __restrict__ qkv, int L, int H, int nblk) {
+template <int HD, bool CROSS>
+__device__ __forceinline__ HeadPtrs head_ptrs(const AttnOps& a, int H, int nblk) {
     HeadPtrs p;
     const int sid = xcd_remap(blockIdx.x, gridDim.x);
     const int bh = sid / nblk;
     p.blk = sid - bh * nblk;
     p.b = bh / H;
     p.h = bh % H;
-    p.rs = (int64_t)3 * H * HD;
     p.ors = (int64_t)H * HD;
-    p.qb = qkv + (int64_t)p.b * L * p.rs + (int64_t)p.h * HD;
-    p.kb = p.qb + p.ors;
-    p.vb = p.kb + p.ors;
+    p.Lq = a.Lq;
+    if constexpr (CROSS) {
+        p.Lk = a.Lk;
+        p.q_rs = a.q_rs, p.k_rs = a.k_rs, p.v_rs = a.v_rs;
+        p.qb = a.q + (int64_t)p.b * p.Lq * p.q_rs + (int64_t)p.h * HD;
+        p.kb = a.k + (int64_t)p.b * p.Lk * p.k_rs + (int64_t)p.h * HD;
+        p.vb = a.v + (int64_t)p.b * p.Lk * p.v_rs + (int64_t)p.h * HD;
+    } else {
+        p.Lk = p.Lq;
+        p.q_rs = p.k_rs = p.v_rs = (int64_t)3 * H * HD;
+        p.qb = a.q + (int64_t)p.b * p.Lq * p.q_rs + (int64_t)p.h * HD;
+        p.kb = p.qb + p.ors;
+        p.vb = p.kb + p.ors;
+    }
     return p;
 }
+// first gradient row of the workgroup's (batch, head) in dq / dk / dv
+template <int HD, bool CROSS>
+__device__ __forceinline__ AttnGrads grad_ptrs(const AttnGrads& g, const HeadPtrs& hp) {
+    AttnGrads r;
+    if constexpr (CROSS) {
+        r.dq_rs = g.dq_rs, r.dk_rs = g.dk_rs, r.dv_rs = g.dv_rs;
+        r.dq = g.dq + (int64_t)hp.b * hp.Lq * r.dq_rs + (int64_t)hp.h * HD;
+        r.dk = g.dk + (int64_t)hp.b * hp.Lk * r.dk_rs + (int64_t)hp.h * HD;
+        r.dv = g.dv + (int64_t)hp.b * hp.Lk * r.dv_rs + (int64_t)hp.h * HD;
+    } else {
+        r.dq_rs = r.dk_rs = r.dv_rs = hp.q_rs;
+        r.dq = g.dq + (int64_t)hp.b * hp.Lq * hp.q_rs + (int64_t)hp.h * HD;
+        r.dk = r.dq + hp.ors;
+        r.dv = r.dk + hp.ors;
+    }
+    return r;
+}
 
-// K and V tile t into LDS buffer `buf` ([buffer 0: K | V][buffer 1: K | V]) for the forward and dQ sweeps
-template <int HD>
-__device__ __forceinline__ void stage_kv(const HeadPtrs hp, const unsigned (&soff)[AG<HD>::CH / 4], int t, int buf, int nfull, int L, unsigned sbase,
-                                         int tid, int wave) {
+// K and V tile t into LDS buffer `buf` ([buffer 0: K | V][buffer 1: K | V]) for the forward and dQ sweeps.  koff / voff: the lane
+// offsets of stage_offsets for the K and the V stride (packed: one array, V's tile is K's moved by one operand width).
+template <int HD, bool CROSS>
+__device__ __forceinline__ void stage_kv(const HeadPtrs hp, const unsigned (&koff)[AG<HD>::CH / 4], const unsigned (&voff)[AG<HD>::CH / 4], int t, int buf,
+                                         int nfull, unsigned sbase, int tid, int wave) {
     constexpr int TILE = AG<HD>::TILE;
     const unsigned lds = sbase + buf * 2 * TILE;
     if (t < nfull) {              // a full tile: scalar base + invariant lane offsets
-        const bf16_t* kt = hp.kb + (int64_t)t * 64 * hp.rs;
-        stage64_full<HD>(kt, soff, lds, wave);
-        stage64_full<HD>(kt + hp.ors, soff, lds + TILE, wave);
+        const bf16_t* kt = hp.kb + (int64_t)t * 64 * hp.k_rs;
+        stage64_full<HD>(kt, koff, lds, wave);
+        if constexpr (CROSS) stage64_full<HD>(hp.vb + (int64_t)t * 64 * hp.v_rs, voff, lds + TILE, wave);
+        else stage64_full<HD>(kt + hp.ors, koff, lds + TILE, wave);
     } else {                      // the ragged last tile: clamped rows
-        stage64<HD>(hp.kb, hp.rs, t * 64, L, lds, tid, wave);
-        stage64<HD>(hp.vb, hp.rs, t * 64, L, lds + TILE, tid, wave);
+        stage64<HD>(hp.kb, hp.k_rs, t * 64, hp.Lk, lds, tid, wave);
+        stage64<HD>(hp.vb, hp.v_rs, t * 64, hp.Lk, lds + TILE, tid, wave);
     }
 }
 
@@ -178,22 +223,23 @@ __device__ __forceinline__ void fwd_tile(unsigned kl, unsigned vl, const TileAdd
 // CAUSAL (the AR consumer, models/larp_ar.py:186-190 `is_causal=True`): query q attends keys 0..q.  A workgroup stops at the last
 // tile its 128 queries can see; per wave a tile is plain (every key <= every query of the wave), masked (fwd_tile<TAIL> with
 // the per-lane limit q + 1 in place of L) or skipped.
-template <int HD, bool CAUSAL = false>
-__global__ __launch_bounds__(256, CAUSAL ? 3 : 4) void attn_fwd_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ o, float* __restrict__ lse2,
-                                                           int L, int H, int nblk, float scale_log2e, int q_begin) {
+template <int HD, bool CAUSAL = false, bool CROSS = false>
+__global__ __launch_bounds__(256, CAUSAL ? 3 : 4) void attn_fwd_kernel(const AttnOps ops, bf16_t* __restrict__ o, float* __restrict__ lse2,
+                                                           int H, int nblk, float scale_log2e, int q_begin) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int half = lane >> 5;
-    const HeadPtrs hp = head_ptrs<HD>(qkv, L, H, nblk);
-    // queries q_begin .. L-1 only (q_begin > 0: the last block of a stack, whose other output rows nobody reads); their
-    // outputs go to a COMPACT o [B, L - q_begin, H, HD]; keys are always all L rows; lse2 keeps the full [B, H, L] index
+    const HeadPtrs hp = head_ptrs<HD, CROSS>(ops, H, nblk);
+    const int Lq = hp.Lq, Lk = hp.Lk;
+    // queries q_begin .. Lq-1 only (q_begin > 0: the last block of a stack, whose other output rows nobody reads); their
+    // outputs go to a COMPACT o [B, Lq - q_begin, H, HD]; keys are always all Lk rows; lse2 keeps the full [B, H, Lq] index
     const int q0 = q_begin + hp.blk * 128 + wave * 32;
-    const int Lq = L - q_begin;
+    const int Lo = Lq - q_begin;
 
     constexpr int TILE = AG<HD>::TILE, KS = AG<HD>::KS, DT = AG<HD>::DT;
     bf16x8 qf[KS];
-    load_own<KS>(hp.qb, hp.rs, q0, L, lane, qf);
+    load_own<KS>(hp.qb, hp.q_rs, q0, Lq, lane, qf);
 
     f32x16 oacc[DT];
 #pragma unroll
@@ -202,32 +248,36 @@ __global__ __launch_bounds__(256, CAUSAL ? 3 : 4) void attn_fwd_kernel(const bf1
         for (int r = 0; r < 16; ++r) oacc[dt][r] = 0.f;
     float m = -__builtin_inff(), lsum = 0.f;
 
-    const int nt = (L + 63) / 64, nfull = (L & 63) ? nt - 1 : nt;
+    const int nt = (Lk + 63) / 64, nfull = (Lk & 63) ? nt - 1 : nt;
     const unsigned sbase = __builtin_amdgcn_readfirstlane(lds_addr_of(smem));
     const TileAddr<HD> ad = tile_addr<HD>(lane, sbase);
-    unsigned soff[AG<HD>::CH / 4];
-    stage_offsets<HD>(hp.rs, tid, soff);
-    auto stage = [&](int t, int buf) __attribute__((always_inline)) { stage_kv<HD>(hp, soff, t, buf, nfull, L, sbase, tid, wave); };
+    unsigned koff[AG<HD>::CH / 4], voff[CROSS ? AG<HD>::CH / 4 : 1];
+    stage_offsets<HD>(hp.k_rs, tid, koff);
+    if constexpr (CROSS) stage_offsets<HD>(hp.v_rs, tid, voff);
+    auto stage = [&](int t, int buf) __attribute__((always_inline)) {
+        if constexpr (CROSS) stage_kv<HD, true>(hp, koff, voff, t, buf, nfull, sbase, tid, wave);
+        else stage_kv<HD, false>(hp, koff, koff, t, buf, nfull, sbase, tid, wave);
+    };
     stage(0, 0);
     pin_loaded(qf);
     dma_drain();
     __syncthreads();
 
-    const int q_end = min(L, q_begin + hp.blk * 128 + 128);           // one past the workgroup's last query
+    const int q_end = min(Lq, q_begin + hp.blk * 128 + 128);          // one past the workgroup's last query
     const int nt_c = CAUSAL ? min(nt, (q_end + 63) / 64) : nt;        // CAUSAL: tiles any of its queries can see
     const int nvis = min(nfull, (q0 + 1) / 64);                       // CAUSAL: tiles with every key <= the wave's first query
-    const int lim = min(L, q0 + (lane & 31) + 1);                     // CAUSAL: this lane's query sees keys < lim
+    const int lim = min(Lk, q0 + (lane & 31) + 1);                    // CAUSAL: this lane's query sees keys < lim
     sweep_tiles<CAUSAL>(0, nt_c, nfull, stage, [&](auto ragged, int buf, int t) __attribute__((always_inline)) {
         const unsigned kl = buf * 2 * TILE;
-        if constexpr (!CAUSAL) fwd_tile<HD, decltype(ragged)::value>(kl, kl + TILE, ad, qf, oacc, m, lsum, t * 64, L, scale_log2e, half);
-        else if (t < nvis) fwd_tile<HD, false>(kl, kl + TILE, ad, qf, oacc, m, lsum, t * 64, L, scale_log2e, half);
+        if constexpr (!CAUSAL) fwd_tile<HD, decltype(ragged)::value>(kl, kl + TILE, ad, qf, oacc, m, lsum, t * 64, Lk, scale_log2e, half);
+        else if (t < nvis) fwd_tile<HD, false>(kl, kl + TILE, ad, qf, oacc, m, lsum, t * 64, Lk, scale_log2e, half);
         else if (t * 64 <= q0 + 31) fwd_tile<HD, true>(kl, kl + TILE, ad, qf, oacc, m, lsum, t * 64, lim, scale_log2e, half);
     });
     const float ltot = lsum + __shfl_xor(lsum, 32);
     const int q = q0 + (lane & 31);
-    const bool ok = q < L;
-    store_own<DT>(oacc, 1.0f / ltot, o + (int64_t)hp.b * Lq * hp.ors + (int64_t)hp.h * HD, hp.ors, q - q_begin, ok, half);
-    if (ok && half == 0) lse2[((int64_t)hp.b * H + hp.h) * L + q] = m + __builtin_amdgcn_logf(ltot);  // v_log_f32 = log2
+    const bool ok = q < Lq;
+    store_own<DT>(oacc, 1.0f / ltot, o + (int64_t)hp.b * Lo * hp.ors + (int64_t)hp.h * HD, hp.ors, q - q_begin, ok, half);
+    if (ok && half == 0) lse2[((int64_t)hp.b * H + hp.h) * Lq + q] = m + __builtin_amdgcn_logf(ltot);  // v_log_f32 = log2
 }
 
 template <int HD, bool TAIL>
@@ -271,36 +321,37 @@ __device__ __forceinline__ void dq_tile(unsigned kl, unsigned vl, const TileAddr
 // delta[b,h,q] = sum_d dO[b,q,h,d] * O[b,q,h,d] for its own rows (both operands are one 16-B load per k-step away) and
 // leaves it in `delta` for the dK/dV kernel, which is launched behind this one.
 // ------------------------------------------------------------------------------------------------
-template <int HD, bool CAUSAL = false>
-__global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ o,
+template <int HD, bool CAUSAL = false, bool CROSS = false>
+__global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(const AttnOps ops, const bf16_t* __restrict__ o,
                                                               const bf16_t* __restrict__ dO, const float* __restrict__ lse2,
-                                                              float* __restrict__ delta, bf16_t* __restrict__ dqkv, int L, int H, int nblk,
+                                                              float* __restrict__ delta, const AttnGrads grads, int H, int nblk,
                                                               float scale, float scale_log2e, int q_begin) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int half = lane >> 5;
-    const HeadPtrs hp = head_ptrs<HD>(qkv, L, H, nblk);
-    const int q0 = q_begin + hp.blk * 128 + wave * 32;   // kept queries only; o / dO are compact [B, L - q_begin, H, HD]
-    const int Lq = L - q_begin;
+    const HeadPtrs hp = head_ptrs<HD, CROSS>(ops, H, nblk);
+    const int Lq = hp.Lq, Lk = hp.Lk;
+    const int q0 = q_begin + hp.blk * 128 + wave * 32;   // kept queries only; o / dO are compact [B, Lq - q_begin, H, HD]
+    const int Lo = Lq - q_begin;
     const int q = q0 + (lane & 31);
-    const int qc = q < L ? q : L - 1;
+    const int qc = q < Lq ? q : Lq - 1;
 
     constexpr int TILE = AG<HD>::TILE, KS = AG<HD>::KS, DT = AG<HD>::DT;
     bf16x8 qf[KS], dof[KS];
-    load_own<KS>(hp.qb, hp.rs, q0, L, lane, qf);
-    load_own<KS>(dO + (int64_t)hp.b * Lq * hp.ors + (int64_t)hp.h * HD, hp.ors, q0 - q_begin, Lq, lane, dof);
-    const float my_lse = lse2[((int64_t)hp.b * H + hp.h) * L + qc];
+    load_own<KS>(hp.qb, hp.q_rs, q0, Lq, lane, qf);
+    load_own<KS>(dO + (int64_t)hp.b * Lo * hp.ors + (int64_t)hp.h * HD, hp.ors, q0 - q_begin, Lo, lane, dof);
+    const float my_lse = lse2[((int64_t)hp.b * H + hp.h) * Lq + qc];
     float my_delta = 0.f;
     {
         bf16x8 of[KS];
-        load_own<KS>(o + (int64_t)hp.b * Lq * hp.ors + (int64_t)hp.h * HD, hp.ors, q0 - q_begin, Lq, lane, of);
+        load_own<KS>(o + (int64_t)hp.b * Lo * hp.ors + (int64_t)hp.h * HD, hp.ors, q0 - q_begin, Lo, lane, of);
 #pragma unroll
         for (int s = 0; s < KS; ++s)
 #pragma unroll
             for (int j = 0; j < 8; ++j) my_delta += bf2f(of[s][j]) * bf2f(dof[s][j]);
         my_delta += __shfl_xor(my_delta, 32);   // the two lane halves hold the two halves of every 16-wide k-step
-        if (q < L && half == 0) delta[((int64_t)hp.b * H + hp.h) * L + q] = my_delta;
+        if (q < Lq && half == 0) delta[((int64_t)hp.b * H + hp.h) * Lq + q] = my_delta;
     }
 
     f32x16 dq[DT];
@@ -309,12 +360,16 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(const bf16_t* __res
 #pragma unroll
         for (int r = 0; r < 16; ++r) dq[dt][r] = 0.f;
 
-    const int nt = (L + 63) / 64, nfull = (L & 63) ? nt - 1 : nt;
+    const int nt = (Lk + 63) / 64, nfull = (Lk & 63) ? nt - 1 : nt;
     const unsigned sbase = __builtin_amdgcn_readfirstlane(lds_addr_of(smem));
     const TileAddr<HD> ad = tile_addr<HD>(lane, sbase);
-    unsigned soff[AG<HD>::CH / 4];
-    stage_offsets<HD>(hp.rs, tid, soff);
-    auto stage = [&](int t, int buf) __attribute__((always_inline)) { stage_kv<HD>(hp, soff, t, buf, nfull, L, sbase, tid, wave); };
+    unsigned koff[AG<HD>::CH / 4], voff[CROSS ? AG<HD>::CH / 4 : 1];
+    stage_offsets<HD>(hp.k_rs, tid, koff);
+    if constexpr (CROSS) stage_offsets<HD>(hp.v_rs, tid, voff);
+    auto stage = [&](int t, int buf) __attribute__((always_inline)) {
+        if constexpr (CROSS) stage_kv<HD, true>(hp, koff, voff, t, buf, nfull, sbase, tid, wave);
+        else stage_kv<HD, false>(hp, koff, koff, t, buf, nfull, sbase, tid, wave);
+    };
     stage(0, 0);
     pin_loaded(qf);
     pin_loaded(dof);
@@ -324,17 +379,18 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(const bf16_t* __res
     dma_drain();
     __syncthreads();
 
-    const int q_end = min(L, q_begin + hp.blk * 128 + 128);           // CAUSAL: see attn_fwd_kernel
+    const int q_end = min(Lq, q_begin + hp.blk * 128 + 128);          // CAUSAL: see attn_fwd_kernel
     const int nt_c = CAUSAL ? min(nt, (q_end + 63) / 64) : nt;
     const int nvis = min(nfull, (q0 + 1) / 64);
-    const int lim = min(L, q0 + (lane & 31) + 1);
+    const int lim = min(Lk, q0 + (lane & 31) + 1);
     sweep_tiles<CAUSAL>(0, nt_c, nfull, stage, [&](auto ragged, int buf, int t) __attribute__((always_inline)) {
         const unsigned kl = buf * 2 * TILE;
-        if constexpr (!CAUSAL) dq_tile<HD, decltype(ragged)::value>(kl, kl + TILE, ad, qf, dof, dq, lse_pin, my_delta, t * 64, L, scale_log2e, half);
-        else if (t < nvis) dq_tile<HD, false>(kl, kl + TILE, ad, qf, dof, dq, lse_pin, my_delta, t * 64, L, scale_log2e, half);
+        if constexpr (!CAUSAL) dq_tile<HD, decltype(ragged)::value>(kl, kl + TILE, ad, qf, dof, dq, lse_pin, my_delta, t * 64, Lk, scale_log2e, half);
+        else if (t < nvis) dq_tile<HD, false>(kl, kl + TILE, ad, qf, dof, dq, lse_pin, my_delta, t * 64, Lk, scale_log2e, half);
         else if (t * 64 <= q0 + 31) dq_tile<HD, true>(kl, kl + TILE, ad, qf, dof, dq, lse_pin, my_delta, t * 64, lim, scale_log2e, half);
     });
-    store_own<DT>(dq, scale, dqkv + (int64_t)hp.b * L * hp.rs + (int64_t)hp.h * HD, hp.rs, q, q < L, half);
+    const AttnGrads g = grad_ptrs<HD, CROSS>(grads, hp);
+    store_own<DT>(dq, scale, g.dq, g.dq_rs, q, q < Lq, half);
 }
 
 // one 64-query tile of the dK/dV sweep.  LDS buffer: Q tile | dO tile | lse2[64] | delta[64]
@@ -397,29 +453,30 @@ __device__ __forceinline__ void dkv_tile(unsigned qt_l, unsigned lse_a, const Ti
 // ------------------------------------------------------------------------------------------------
 // dK, dV: own rows = keys; streams Q and dO tiles (both row reads and transposed reads) + lse2/delta
 // ------------------------------------------------------------------------------------------------
-template <int HD, bool CAUSAL = false>
-__global__ __launch_bounds__(256, CAUSAL ? 2 : 3) void attn_bwd_dkv_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dO,
+template <int HD, bool CAUSAL = false, bool CROSS = false>
+__global__ __launch_bounds__(256, CAUSAL ? 2 : 3) void attn_bwd_dkv_kernel(const AttnOps ops, const bf16_t* __restrict__ dO,
                                                                const float* __restrict__ lse2, const float* __restrict__ delta,
-                                                               bf16_t* __restrict__ dqkv, int L, int H, int nblk, float scale, float scale_log2e,
+                                                               const AttnGrads grads, int H, int nblk, float scale, float scale_log2e,
                                                                int q_begin) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int half = lane >> 5;
-    const HeadPtrs hp = head_ptrs<HD>(qkv, L, H, nblk);
-    const int64_t rs = hp.rs, ors = hp.ors;
-    // query tiles from q_begin on (a multiple of 64; the rows before it got no gradient), dO compact [B, L - q_begin, H, HD]
-    const int Lq = L - q_begin;
-    const bf16_t* dob = dO + (int64_t)hp.b * Lq * ors + (int64_t)hp.h * HD;
-    const float* lse_b = lse2 + ((int64_t)hp.b * H + hp.h) * L;
-    const float* del_b = delta + ((int64_t)hp.b * H + hp.h) * L;
+    const HeadPtrs hp = head_ptrs<HD, CROSS>(ops, H, nblk);
+    const int64_t rs = hp.q_rs, ors = hp.ors;
+    const int Lq = hp.Lq, Lk = hp.Lk;
+    // query tiles from q_begin on (a multiple of 64; the rows before it got no gradient), dO compact [B, Lq - q_begin, H, HD]
+    const int Lo = Lq - q_begin;
+    const bf16_t* dob = dO + (int64_t)hp.b * Lo * ors + (int64_t)hp.h * HD;
+    const float* lse_b = lse2 + ((int64_t)hp.b * H + hp.h) * Lq;
+    const float* del_b = delta + ((int64_t)hp.b * H + hp.h) * Lq;
     const int k0 = hp.blk * 128 + wave * 32;
     const int key = k0 + (lane & 31);
 
     constexpr int TILE = AG<HD>::TILE, KS = AG<HD>::KS, DT = AG<HD>::DT;
     bf16x8 kf[KS], vf[KS];
-    load_own<KS>(hp.kb, rs, k0, L, lane, kf);
-    load_own<KS>(hp.vb, rs, k0, L, lane, vf);
+    load_own<KS>(hp.kb, hp.k_rs, k0, Lk, lane, kf);
+    load_own<KS>(hp.vb, hp.v_rs, k0, Lk, lane, vf);
 
     f32x16 dk[DT], dv[DT];
 #pragma unroll
@@ -429,7 +486,7 @@ __global__ __launch_bounds__(256, CAUSAL ? 2 : 3) void attn_bwd_dkv_kernel(const
 
     // LDS: per buffer  Q tile | dO tile | lse2[64] | delta[64]
     constexpr int BUF = 2 * TILE + 512;
-    const int nt = (L + 63) / 64, nfull = (L & 63) ? nt - 1 : nt;
+    const int nt = (Lq + 63) / 64, nfull = (Lq & 63) ? nt - 1 : nt;
     const unsigned sbase = __builtin_amdgcn_readfirstlane(lds_addr_of(smem));
     const TileAddr<HD> ad = tile_addr<HD>(lane, sbase);
     unsigned lse_a = sbase + 16 * half;
@@ -437,19 +494,19 @@ __global__ __launch_bounds__(256, CAUSAL ? 2 : 3) void attn_bwd_dkv_kernel(const
     unsigned qoff[AG<HD>::CH / 4], dooff[AG<HD>::CH / 4];
     stage_offsets<HD>(rs, tid, qoff);
     stage_offsets<HD>(ors, tid, dooff);
-    const int nfull_q = L / 64;        // query tiles without a ragged row
+    const int nfull_q = Lq / 64;       // query tiles without a ragged row
     auto stage = [&](int t, int buf) __attribute__((always_inline)) {
         const unsigned base = sbase + buf * BUF;
         if (t < nfull_q) {
             stage64_full<HD>(hp.qb + (int64_t)t * 64 * rs, qoff, base, wave);
             stage64_full<HD>(dob + ((int64_t)t * 64 - q_begin) * ors, dooff, base + TILE, wave);
         } else {
-            stage64<HD>(hp.qb, rs, t * 64, L, base, tid, wave);
-            stage64<HD>(dob, ors, t * 64 - q_begin, Lq, base + TILE, tid, wave);
+            stage64<HD>(hp.qb, rs, t * 64, Lq, base, tid, wave);
+            stage64<HD>(dob, ors, t * 64 - q_begin, Lo, base + TILE, tid, wave);
         }
-        if (wave < 2) {  // wave 0: lse2[64], wave 1: delta[64] by 4-byte LDS-DMA (rows past L clamped; masked at use)
+        if (wave < 2) {  // wave 0: lse2[64], wave 1: delta[64] by 4-byte LDS-DMA (rows past Lq clamped; masked at use)
             int qq = t * 64 + lane;
-            qq = qq < L ? qq : L - 1;
+            qq = qq < Lq ? qq : Lq - 1;
             glds4_asm((wave == 0 ? lse_b : del_b) + qq, base + 2 * TILE + wave * 256);
         }
     };
@@ -462,13 +519,13 @@ __global__ __launch_bounds__(256, CAUSAL ? 2 : 3) void attn_bwd_dkv_kernel(const
     __syncthreads();
 
     sweep_tiles<CAUSAL>(t0, nt, nfull, stage, [&](auto ragged, int buf, int t) __attribute__((always_inline)) {
-        if constexpr (!CAUSAL) dkv_tile<HD, decltype(ragged)::value>(buf * BUF, lse_a, ad, kf, vf, dk, dv, t * 64, L, scale_log2e, half);
-        else if (t < nfull && t * 64 >= k0 + 31) dkv_tile<HD, false>(buf * BUF, lse_a, ad, kf, vf, dk, dv, t * 64, L, scale_log2e, half);
-        else if (t * 64 + 63 >= k0) dkv_tile<HD, true, true>(buf * BUF, lse_a, ad, kf, vf, dk, dv, t * 64, L, scale_log2e, half, key);
+        if constexpr (!CAUSAL) dkv_tile<HD, decltype(ragged)::value>(buf * BUF, lse_a, ad, kf, vf, dk, dv, t * 64, Lq, scale_log2e, half);
+        else if (t < nfull && t * 64 >= k0 + 31) dkv_tile<HD, false>(buf * BUF, lse_a, ad, kf, vf, dk, dv, t * 64, Lq, scale_log2e, half);
+        else if (t * 64 + 63 >= k0) dkv_tile<HD, true, true>(buf * BUF, lse_a, ad, kf, vf, dk, dv, t * 64, Lq, scale_log2e, half, key);
     });
-    bf16_t* dkb = dqkv + (int64_t)hp.b * L * rs + (int64_t)hp.h * HD + ors;
-    store_own<DT>(dk, scale, dkb, rs, key, key < L, half);
-    store_own<DT>(dv, 1.0f, dkb + ors, rs, key, key < L, half);
+    const AttnGrads g = grad_ptrs<HD, CROSS>(grads, hp);
+    store_own<DT>(dk, scale, g.dk, g.dk_rs, key, key < Lk, half);
+    store_own<DT>(dv, 1.0f, g.dv, g.dv_rs, key, key < Lk, half);
 }
 
 // dQ rows of the queries before q_begin: they received no gradient (the dQ kernel only visits the kept queries)
@@ -492,25 +549,28 @@ constexpr float kScale = HD == 64 ? 0.125f : 0.17677669529663688110f;
 template <int HD>
 constexpr float kScaleLog2e = kScale<HD> * 1.44269504088896340736f;
 
-template <int HD, bool CAUSAL = false>
-static void launch_fwd(const void* qkv, int B, int L, int H, int q_begin, void* o, float* lse2, hipStream_t s) {
-    const int nblk = (L - q_begin + 127) / 128;
-    hipLaunchKernelGGL((attn_fwd_kernel<HD, CAUSAL>), dim3(nblk * B * H), dim3(256), 4 * AG<HD>::TILE, s, (const bf16_t*)qkv, (bf16_t*)o, lse2, L, H, nblk,
+static AttnOps packed_ops(const void* qkv, int L) { return AttnOps{(const bf16_t*)qkv, nullptr, nullptr, 0, 0, 0, L, L}; }
+static AttnGrads packed_grads(void* dqkv) { return AttnGrads{(bf16_t*)dqkv, nullptr, nullptr, 0, 0, 0}; }
+
+template <int HD, bool CAUSAL = false, bool CROSS = false>
+static void launch_fwd(const AttnOps& ops, int B, int H, int q_begin, void* o, float* lse2, hipStream_t s) {
+    const int nblk = (ops.Lq - q_begin + 127) / 128;
+    hipLaunchKernelGGL((attn_fwd_kernel<HD, CAUSAL, CROSS>), dim3(nblk * B * H), dim3(256), 4 * AG<HD>::TILE, s, ops, (bf16_t*)o, lse2, H, nblk,
                        kScaleLog2e<HD>, q_begin);
 }
 
-template <int HD, bool CAUSAL = false>
-static void launch_bwd(const void* qkv, const void* o, const void* dO, const float* lse2, int B, int L, int H, int q_begin, void* dqkv,
+template <int HD, bool CAUSAL = false, bool CROSS = false>
+static void launch_bwd(const AttnOps& ops, const void* o, const void* dO, const float* lse2, int B, int H, int q_begin, const AttnGrads& grads,
                        float* delta_ws, hipStream_t s) {
-    if (q_begin > 0) {
+    if (q_begin > 0) {   // packed launches only
         const int64_t n = (int64_t)B * q_begin * (H * HD / 8);
-        hipLaunchKernelGGL(zero_q_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (bf16_t*)dqkv, L, q_begin, (int64_t)3 * H * HD, H * HD);
+        hipLaunchKernelGGL(zero_q_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, grads.dq, ops.Lq, q_begin, (int64_t)3 * H * HD, H * HD);
     }
-    const int nblk_q = (L - q_begin + 127) / 128, nblk_k = (L + 127) / 128;
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<HD, CAUSAL>), dim3(nblk_q * B * H), dim3(256), 4 * AG<HD>::TILE, s, (const bf16_t*)qkv, (const bf16_t*)o,
-                       (const bf16_t*)dO, lse2, delta_ws, (bf16_t*)dqkv, L, H, nblk_q, kScale<HD>, kScaleLog2e<HD>, q_begin);
-    hipLaunchKernelGGL((attn_bwd_dkv_kernel<HD, CAUSAL>), dim3(nblk_k * B * H), dim3(256), 2 * (2 * AG<HD>::TILE + 512), s, (const bf16_t*)qkv,
-                       (const bf16_t*)dO, lse2, delta_ws, (bf16_t*)dqkv, L, H, nblk_k, kScale<HD>, kScaleLog2e<HD>, q_begin);
+    const int nblk_q = (ops.Lq - q_begin + 127) / 128, nblk_k = (ops.Lk + 127) / 128;
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<HD, CAUSAL, CROSS>), dim3(nblk_q * B * H), dim3(256), 4 * AG<HD>::TILE, s, ops, (const bf16_t*)o,
+                       (const bf16_t*)dO, lse2, delta_ws, grads, H, nblk_q, kScale<HD>, kScaleLog2e<HD>, q_begin);
+    hipLaunchKernelGGL((attn_bwd_dkv_kernel<HD, CAUSAL, CROSS>), dim3(nblk_k * B * H), dim3(256), 2 * (2 * AG<HD>::TILE + 512), s, ops,
+                       (const bf16_t*)dO, lse2, delta_ws, grads, H, nblk_k, kScale<HD>, kScaleLog2e<HD>, q_begin);
 }
 
 // every operand is read and every output written 16 bytes per lane (the outputs since the widened stores of round 5)
@@ -531,8 +591,8 @@ extern "C" int vt_attention_fwd_rows(const void* qkv, int32_t B, int32_t L, int3
     VT_CHECK_ARG(attn_aligned(qkv, o_compact), "vt_attention_fwd: qkv and o must be 16-byte aligned");
     int rc = attn_check("vt_attention_fwd", B, L, H, hd, q_begin);
     if (rc) return rc;
-    if (hd == 64) launch_fwd<64>(qkv, B, L, H, q_begin, o_compact, lse2, (hipStream_t)stream);
-    else launch_fwd<32>(qkv, B, L, H, q_begin, o_compact, lse2, (hipStream_t)stream);
+    if (hd == 64) launch_fwd<64>(packed_ops(qkv, L), B, H, q_begin, o_compact, lse2, (hipStream_t)stream);
+    else launch_fwd<32>(packed_ops(qkv, L), B, H, q_begin, o_compact, lse2, (hipStream_t)stream);
     VT_CHECK_LAUNCH("vt_attention_fwd");
     return VT_OK;
 }
@@ -543,8 +603,8 @@ extern "C" int vt_attention_bwd_rows(const void* qkv, const void* o_compact, con
     VT_CHECK_ARG(attn_aligned(qkv, o_compact, dO_compact, dqkv), "vt_attention_bwd: qkv, o, dO and dqkv must be 16-byte aligned");
     int rc = attn_check("vt_attention_bwd", B, L, H, hd, q_begin);
     if (rc) return rc;
-    if (hd == 64) launch_bwd<64>(qkv, o_compact, dO_compact, lse2, B, L, H, q_begin, dqkv, delta_ws, (hipStream_t)stream);
-    else launch_bwd<32>(qkv, o_compact, dO_compact, lse2, B, L, H, q_begin, dqkv, delta_ws, (hipStream_t)stream);
+    if (hd == 64) launch_bwd<64>(packed_ops(qkv, L), o_compact, dO_compact, lse2, B, H, q_begin, packed_grads(dqkv), delta_ws, (hipStream_t)stream);
+    else launch_bwd<32>(packed_ops(qkv, L), o_compact, dO_compact, lse2, B, H, q_begin, packed_grads(dqkv), delta_ws, (hipStream_t)stream);
     VT_CHECK_LAUNCH("vt_attention_bwd");
     return VT_OK;
 }
@@ -566,7 +626,7 @@ extern "C" int vt_attention_causal_fwd(const void* qkv, int32_t B, int32_t L, in
     VT_CHECK_ARG(qkv && o && lse2, "vt_attention_causal_fwd: null pointer");
     VT_CHECK_ARG(B > 0 && L > 0 && H > 0, "vt_attention_causal_fwd: bad shape");
     VT_CHECK_ARG(attn_aligned(qkv, o), "vt_attention_causal_fwd: qkv and o must be 16-byte aligned");
-    launch_fwd<64, true>(qkv, B, L, H, 0, o, lse2, (hipStream_t)stream);
+    launch_fwd<64, true>(packed_ops(qkv, L), B, H, 0, o, lse2, (hipStream_t)stream);
     VT_CHECK_LAUNCH("vt_attention_causal_fwd");
     return VT_OK;
 }
@@ -576,7 +636,60 @@ extern "C" int vt_attention_causal_bwd(const void* qkv, const void* o, const voi
     VT_CHECK_ARG(qkv && o && dO && lse2 && dqkv && delta_ws, "vt_attention_causal_bwd: null pointer");
     VT_CHECK_ARG(B > 0 && L > 0 && H > 0, "vt_attention_causal_bwd: bad shape");
     VT_CHECK_ARG(attn_aligned(qkv, o, dO, dqkv), "vt_attention_causal_bwd: qkv, o, dO and dqkv must be 16-byte aligned");
-    launch_bwd<64, true>(qkv, o, dO, lse2, B, L, H, 0, dqkv, delta_ws, (hipStream_t)stream);
+    launch_bwd<64, true>(packed_ops(qkv, L), o, dO, lse2, B, H, 0, packed_grads(dqkv), delta_ws, (hipStream_t)stream);
     VT_CHECK_LAUNCH("vt_attention_causal_bwd");
+    return VT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// cross attention: queries from one tensor, keys and values from another (CrossAttention.forward of
+// models/model_design/base/transformer.py:127-141: flash_attn_func(q, k, v) with Lq != Lk); head_dim 64, no mask
+// ------------------------------------------------------------------------------------------------
+static int cross_check(const char* who, int B, int Lq, int Lk, int H, int hd) {
+    VT_CHECK_ARG(hd == 64, "%s: head_dim %d unsupported (64)", who, hd);
+    VT_CHECK_ARG(B > 0 && Lq > 0 && Lk > 0 && H > 0, "%s: bad shape B=%d Lq=%d Lk=%d H=%d", who, B, Lq, Lk, H);
+    VT_CHECK_ARG((int64_t)B * H * ((Lq > Lk ? Lq : Lk) / 128 + 1) <= 0x7fffffff, "%s: too many workgroups", who);
+    return VT_OK;
+}
+static int cross_stride_check(const char* who, const char* what, int64_t rs, int H) {
+    VT_CHECK_ARG(rs >= (int64_t)64 * H && rs % 8 == 0, "%s: row stride %lld of %s must cover 64 x %d columns and be a multiple of 8", who, (long long)rs,
+                 what, H);
+    // the tile stagers fold (row within a 64-row tile) * rs * 2 bytes into a 32-bit lane offset: below 2^31 with rs < 2^24
+    VT_CHECK_ARG(rs < ((int64_t)1 << 24), "%s: row stride %lld of %s is too large (below 2^24 elements)", who, (long long)rs, what);
+    return VT_OK;
+}
+
+extern "C" int vt_attention_cross_fwd(const void* q, int64_t q_rs, const void* k, int64_t k_rs, const void* v, int64_t v_rs, int32_t B, int32_t Lq,
+                                      int32_t Lk, int32_t H, int32_t hd, void* o, float* lse2, vtStream stream) {
+    const char* who = "vt_attention_cross_fwd";
+    VT_CHECK_ARG(q && k && v && o && lse2, "%s: null pointer", who);
+    TRY(cross_check(who, B, Lq, Lk, H, hd));
+    TRY(cross_stride_check(who, "q", q_rs, H));
+    TRY(cross_stride_check(who, "k", k_rs, H));
+    TRY(cross_stride_check(who, "v", v_rs, H));
+    VT_CHECK_ARG(attn_aligned(q, k, v, o), "%s: q, k, v and o must be 16-byte aligned", who);
+    const AttnOps ops{(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, q_rs, k_rs, v_rs, Lq, Lk};
+    launch_fwd<64, false, true>(ops, B, H, 0, o, lse2, (hipStream_t)stream);
+    VT_CHECK_LAUNCH(who);
+    return VT_OK;
+}
+
+extern "C" int vt_attention_cross_bwd(const void* q, int64_t q_rs, const void* k, int64_t k_rs, const void* v, int64_t v_rs, const void* o,
+                                      const void* dO, const float* lse2, int32_t B, int32_t Lq, int32_t Lk, int32_t H, int32_t hd, void* dq,
+                                      int64_t dq_rs, void* dk, int64_t dk_rs, void* dv, int64_t dv_rs, float* delta_ws, vtStream stream) {
+    const char* who = "vt_attention_cross_bwd";
+    VT_CHECK_ARG(q && k && v && o && dO && lse2 && dq && dk && dv && delta_ws, "%s: null pointer", who);
+    TRY(cross_check(who, B, Lq, Lk, H, hd));
+    TRY(cross_stride_check(who, "q", q_rs, H));
+    TRY(cross_stride_check(who, "k", k_rs, H));
+    TRY(cross_stride_check(who, "v", v_rs, H));
+    TRY(cross_stride_check(who, "dq", dq_rs, H));
+    TRY(cross_stride_check(who, "dk", dk_rs, H));
+    TRY(cross_stride_check(who, "dv", dv_rs, H));
+    VT_CHECK_ARG(attn_aligned(q, k, v, o) && attn_aligned(dO, dq, dk, dv), "%s: q, k, v, o, dO, dq, dk and dv must be 16-byte aligned", who);
+    const AttnOps ops{(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, q_rs, k_rs, v_rs, Lq, Lk};
+    const AttnGrads grads{(bf16_t*)dq, (bf16_t*)dk, (bf16_t*)dv, dq_rs, dk_rs, dv_rs};
+    launch_bwd<64, false, true>(ops, o, dO, lse2, B, H, 0, grads, delta_ws, (hipStream_t)stream);
+    VT_CHECK_LAUNCH(who);
     return VT_OK;
 }

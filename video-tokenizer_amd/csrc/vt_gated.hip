@@ -6,7 +6,8 @@
 // The GEMMs, the LayerNorm over D and the attention itself are the kernels of the LARP path; what is new here is
 // HBM-bound glue, each a single pass with 16-byte accesses:
 //   qknorm_rope   reads q|k|v of the packed [M, 4D] projection, writes the packed [M, 3D] operand of vt_attention_*
-//   sigmoid_gate  o * sigmoid(gate), gate read in place from columns 3D..4D of the projection
+//   sigmoid_gate  o * sigmoid(gate), gate read in place from columns 3D..4D of the projection (vt_sigmoid_gate_cols_*: from any
+//                 column block of any projection -- CrossAttention of model_design reads it from columns D..2D of [to_q ; to_gate])
 //   geglu         gelu(h[:, I:]) * h[:, :I]
 // and their backward passes, which write straight into the [M, 4D] / [M, 2I] gradient of the projection so no torch
 // cat/chunk copies are needed.  Rounding points follow autocast(bf16): LayerNorm output, rotary output, sigmoid, gelu and
@@ -169,12 +170,14 @@ __global__ __launch_bounds__(256) void qknorm_reduce_kernel(const float* __restr
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + __expf(-x)); }
 
-__global__ __launch_bounds__(256) void gate_fwd_kernel(const bf16_t* __restrict__ o, const bf16_t* __restrict__ qkvg, int64_t M, int D, bf16_t* __restrict__ og) {
+// gate: first gate column of row 0, gate_rs its row stride (the block's gate is qkvg + 3D with stride 4D; vt_sigmoid_gate_cols_* takes any)
+__global__ __launch_bounds__(256) void gate_fwd_kernel(const bf16_t* __restrict__ o, const bf16_t* __restrict__ gate, int64_t gate_rs, int64_t M, int D,
+                                                        bf16_t* __restrict__ og) {
     const int64_t per_row = D / 8, total = M * per_row;
     for (int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x; u < total; u += (int64_t)gridDim.x * 256) {
         const int64_t row = u / per_row;
         const int col = (int)(u % per_row) * 8;
-        const Vec8 a = load8(o + row * D + col), g = load8(qkvg + row * 4 * D + 3 * (int64_t)D + col);
+        const Vec8 a = load8(o + row * D + col), g = load8(gate + row * gate_rs + col);
         Vec8 r;
 #pragma unroll
         for (int i = 0; i < 8; ++i) r.v[i] = a.v[i] * round_bf16(sigmoidf_(g.v[i]));
@@ -182,13 +185,14 @@ __global__ __launch_bounds__(256) void gate_fwd_kernel(const bf16_t* __restrict_
     }
 }
 
-__global__ __launch_bounds__(256) void gate_bwd_kernel(const bf16_t* __restrict__ dog, const bf16_t* __restrict__ o, const bf16_t* __restrict__ qkvg, int64_t M,
-                                                        int D, bf16_t* __restrict__ d_o, bf16_t* __restrict__ dqkvg) {
+__global__ __launch_bounds__(256) void gate_bwd_kernel(const bf16_t* __restrict__ dog, const bf16_t* __restrict__ o, const bf16_t* __restrict__ gate,
+                                                        int64_t gate_rs, int64_t M, int D, bf16_t* __restrict__ d_o, bf16_t* __restrict__ dgate,
+                                                        int64_t dgate_rs) {
     const int64_t per_row = D / 8, total = M * per_row;
     for (int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x; u < total; u += (int64_t)gridDim.x * 256) {
         const int64_t row = u / per_row;
         const int col = (int)(u % per_row) * 8;
-        const Vec8 dy = load8(dog + row * D + col), a = load8(o + row * D + col), g = load8(qkvg + row * 4 * D + 3 * (int64_t)D + col);
+        const Vec8 dy = load8(dog + row * D + col), a = load8(o + row * D + col), g = load8(gate + row * gate_rs + col);
         Vec8 da, dg;
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
@@ -197,7 +201,7 @@ __global__ __launch_bounds__(256) void gate_bwd_kernel(const bf16_t* __restrict_
             dg.v[i] = round_bf16(dy.v[i] * a.v[i]) * ((1.0f - sg) * sg);
         }
         store8(d_o + row * D + col, da);
-        store8(dqkvg + row * 4 * D + 3 * (int64_t)D + col, dg);
+        store8(dgate + row * dgate_rs + col, dg);
     }
 }
 
@@ -269,21 +273,47 @@ extern "C" int vt_qknorm_rope_bwd(const void* qkvg, const void* dqkv, int64_t M,
     return VT_OK;
 }
 
+// `who`: the entry point's name, so that a refusal or a launch failure is reported under the caller's own name
+static int gate_cols_fwd(const char* who, const void* o, const void* gate, int64_t gate_rs, int64_t M, int32_t D, void* og, vtStream stream) {
+    VT_CHECK_ARG(o && gate && og && M > 0 && D > 0 && D % 8 == 0, "%s: null pointer or D %% 8 != 0", who);
+    VT_CHECK_ARG(gate_rs >= D && gate_rs % 8 == 0, "%s: gate row stride %lld must be >= D = %d and a multiple of 8", who, (long long)gate_rs, D);
+    VT_CHECK_ARG(aligned16(o) && aligned16(gate) && aligned16(og), "%s: buffers must be 16-byte aligned", who);
+    hipLaunchKernelGGL(gate_fwd_kernel, dim3(grid_for(M * (D / 8))), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)o, (const bf16_t*)gate, gate_rs, M, D,
+                       (bf16_t*)og);
+    VT_CHECK_LAUNCH(who);
+    return VT_OK;
+}
+extern "C" int vt_sigmoid_gate_cols_fwd(const void* o, const void* gate, int64_t gate_rs, int64_t M, int32_t D, void* og, vtStream stream) {
+    return gate_cols_fwd("vt_sigmoid_gate_cols_fwd", o, gate, gate_rs, M, D, og, stream);
+}
+
+static int gate_cols_bwd(const char* who, const void* dog, const void* o, const void* gate, int64_t gate_rs, int64_t M, int32_t D, void* d_o, void* dgate,
+                         int64_t dgate_rs, vtStream stream) {
+    VT_CHECK_ARG(dog && o && gate && d_o && dgate && M > 0 && D > 0 && D % 8 == 0, "%s: null pointer or D %% 8 != 0", who);
+    VT_CHECK_ARG(gate_rs >= D && gate_rs % 8 == 0 && dgate_rs >= D && dgate_rs % 8 == 0, "%s: gate row strides %lld, %lld must be >= D = %d and multiples of 8", who,
+                 (long long)gate_rs, (long long)dgate_rs, D);
+    VT_CHECK_ARG(aligned16(dog) && aligned16(o) && aligned16(gate) && aligned16(d_o) && aligned16(dgate), "%s: buffers must be 16-byte aligned", who);
+    hipLaunchKernelGGL(gate_bwd_kernel, dim3(grid_for(M * (D / 8))), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dog, (const bf16_t*)o,
+                       (const bf16_t*)gate, gate_rs, M, D, (bf16_t*)d_o, (bf16_t*)dgate, dgate_rs);
+    VT_CHECK_LAUNCH(who);
+    return VT_OK;
+}
+extern "C" int vt_sigmoid_gate_cols_bwd(const void* dog, const void* o, const void* gate, int64_t gate_rs, int64_t M, int32_t D, void* d_o, void* dgate,
+                                        int64_t dgate_rs, vtStream stream) {
+    return gate_cols_bwd("vt_sigmoid_gate_cols_bwd", dog, o, gate, gate_rs, M, D, d_o, dgate, dgate_rs, stream);
+}
+
+// the block's layout: the gate is columns 3D..4D of the [M, 4D] projection, its gradient the same columns of dqkvg
 extern "C" int vt_sigmoid_gate_fwd(const void* o, const void* qkvg, int64_t M, int32_t D, void* og, vtStream stream) {
     VT_CHECK_ARG(o && qkvg && og && M > 0 && D > 0 && D % 8 == 0, "vt_sigmoid_gate_fwd: null pointer or D %% 8 != 0");
     VT_CHECK_ARG(aligned16(o) && aligned16(qkvg) && aligned16(og), "vt_sigmoid_gate_fwd: buffers must be 16-byte aligned");
-    hipLaunchKernelGGL(gate_fwd_kernel, dim3(grid_for(M * (D / 8))), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)o, (const bf16_t*)qkvg, M, D, (bf16_t*)og);
-    VT_CHECK_LAUNCH("vt_sigmoid_gate_fwd");
-    return VT_OK;
+    return gate_cols_fwd("vt_sigmoid_gate_fwd", o, (const bf16_t*)qkvg + 3 * (int64_t)D, 4 * (int64_t)D, M, D, og, stream);
 }
 
 extern "C" int vt_sigmoid_gate_bwd(const void* dog, const void* o, const void* qkvg, int64_t M, int32_t D, void* d_o, void* dqkvg, vtStream stream) {
     VT_CHECK_ARG(dog && o && qkvg && d_o && dqkvg && M > 0 && D > 0 && D % 8 == 0, "vt_sigmoid_gate_bwd: null pointer or D %% 8 != 0");
     VT_CHECK_ARG(aligned16(dog) && aligned16(o) && aligned16(qkvg) && aligned16(d_o) && aligned16(dqkvg), "vt_sigmoid_gate_bwd: buffers must be 16-byte aligned");
-    hipLaunchKernelGGL(gate_bwd_kernel, dim3(grid_for(M * (D / 8))), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dog, (const bf16_t*)o,
-                       (const bf16_t*)qkvg, M, D, (bf16_t*)d_o, (bf16_t*)dqkvg);
-    VT_CHECK_LAUNCH("vt_sigmoid_gate_bwd");
-    return VT_OK;
+    return gate_cols_bwd("vt_sigmoid_gate_bwd", dog, o, (const bf16_t*)qkvg + 3 * (int64_t)D, 4 * (int64_t)D, M, D, d_o, (bf16_t*)dqkvg + 3 * (int64_t)D, 4 * (int64_t)D, stream);
 }
 
 extern "C" int vt_geglu_fwd(const void* h, int64_t M, int32_t I, void* a, int64_t lda, vtStream stream) {

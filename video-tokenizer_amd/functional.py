@@ -417,3 +417,109 @@ class Unpatchify(torch.autograd.Function):
     def backward(ctx, dvideo):
         B, C, T, S, pt, p = ctx.geom
         return hip.patchify(dvideo.contiguous().float(), pt, p).float(), None
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# cross attention and model_design's CrossAttention layer (models/model_design/base/transformer.py:92-141)
+# ------------------------------------------------------------------------------------------------------------------------
+def _rows64(*ts):
+    """the weight-gradient GEMMs contract over rows in steps of 64: zero-padded copies of ragged row counts"""
+    M = ts[0].shape[0]
+    if M % 64 == 0:
+        return ts
+    out = []
+    for t in ts:
+        z = torch.zeros(_pad64(M), t.shape[1], device=t.device, dtype=t.dtype)
+        z[:M].copy_(t)
+        out.append(z)
+    return out
+
+
+class CrossAttend(torch.autograd.Function):
+    """softmax(q k^T / 8) v, head_dim 64, no mask, on vt_attention_cross_*: q a bf16 view [B * Lq, 64 H], k and v bf16 views [B * Lk, 64 H],
+    each with a row stride of its own (column blocks of wider projections are read in place) -> o bf16 [B * Lq, 64 H]"""
+
+    @staticmethod
+    def forward(ctx, q, k, v, B, Lq, Lk, H):
+        o, lse2 = hip.attention_cross_fwd(q, k, v, B, Lq, Lk, H)
+        ctx.save_for_backward(q, k, v, o, lse2)
+        ctx.geom = (B, Lq, Lk, H)
+        return o
+
+    @staticmethod
+    def backward(ctx, dO):
+        q, k, v, o, lse2 = ctx.saved_tensors
+        dq, dk, dv = hip.attention_cross_bwd(q, k, v, o, dO.contiguous().to(torch.bfloat16), lse2, *ctx.geom)
+        return dq, dk, dv, None, None, None, None
+
+
+class CrossAttentionLayer(torch.autograd.Function):
+    """CrossAttention.forward (models/model_design/base/transformer.py:118-141) on x fp32 [B, Lq, D], context fp32 [B, Lk, Dc], D = 64 H,
+    as nine launches: rmsnorm_any(x); ONE GEMM on [to_q ; to_gate] (N = 2D); rmsnorm_any(context); the to_kv GEMM; head RMSNorm of q and
+    of k; vt_attention_cross_fwd with v read in place from the to_kv output; the gate from columns D..2D of the first GEMM; out_proj.
+    Rounding points of autocast(bf16): bf16 Linear outputs, bf16 attention output and gate product, fp32 x / context and input gradients.
+    pk_*: (bf16 [N, K], bf16 [K, N]) operand copies of [to_q ; to_gate], to_kv and out_proj (hip.pack_weight)."""
+
+    @staticmethod
+    def forward(ctx, x, context, norm_q_w, norm_kv_w, to_q_w, to_kv_w, to_gate_w, q_norm_w, k_norm_w, out_proj_w, H, eps, pk_qg, pk_kv, pk_o):
+        hip.require_gpu(x, context, norm_q_w, norm_kv_w, to_q_w, to_kv_w, to_gate_w, q_norm_w, k_norm_w, out_proj_w)
+        B, Lq, D = x.shape
+        Lk, Dc = context.shape[1], context.shape[2]
+        assert context.shape[0] == B and D == 64 * H and to_kv_w.shape == (2 * D, Dc)
+        x2 = x.contiguous().reshape(B * Lq, D).float()
+        c2 = context.contiguous().reshape(B * Lk, Dc).float()
+        nq_w, nkv_w, qn_w, kn_w = (t.detach().float().contiguous() for t in (norm_q_w, norm_kv_w, q_norm_w, k_norm_w))
+        xn, rstd_x = hip.rmsnorm_any_fwd(x2, nq_w, eps)
+        qg = hip.gemm_nt(xn, pk_qg[0], hip.EPI_BF16)                    # [Mq, 2D] = [to_q xn | to_gate xn]
+        cn, rstd_c = hip.rmsnorm_any_fwd(c2, nkv_w, eps)
+        kv = hip.gemm_nt(cn, pk_kv[0], hip.EPI_BF16)                    # [Mk, 2D] = [k | v]
+        qn = hip.head_rmsnorm_fwd(qg[:, :D], qn_w, eps, H)
+        kn = hip.head_rmsnorm_fwd(kv[:, :D], kn_w, eps, H)
+        o, lse2 = hip.attention_cross_fwd(qn, kn, kv[:, D:], B, Lq, Lk, H)
+        og = hip.sigmoid_gate_cols_fwd(o, qg[:, D:])
+        out = hip.gemm_nt(og, pk_o[0], hip.EPI_F32, round_bf16=True)
+        ctx.save_for_backward(x2, c2, nq_w, nkv_w, qn_w, kn_w, rstd_x, rstd_c, xn, cn, qg, kv, qn, kn, o, lse2, og, pk_qg[1], pk_kv[1], pk_o[1])
+        ctx.geom = (B, Lq, Lk, D, Dc, H, eps)
+        return out.reshape(B, Lq, D)
+
+    @staticmethod
+    def backward(ctx, dout):
+        x2, c2, nq_w, nkv_w, qn_w, kn_w, rstd_x, rstd_c, xn, cn, qg, kv, qn, kn, o, lse2, og, wqg_t, wkv_t, wo_t = ctx.saved_tensors
+        B, Lq, Lk, D, Dc, H, eps = ctx.geom
+        Mq, Mk = B * Lq, B * Lk
+        dev = dout.device
+        need = ctx.needs_input_grad
+        gb = hip.cast_rows(dout.contiguous().reshape(Mq, D).float())
+        dog = hip.gemm_nt(gb, wo_t, hip.EPI_BF16)
+        dqg = torch.empty(Mq, 2 * D, device=dev, dtype=torch.bfloat16)   # gradient of [q | gate], every column written below
+        dkv = torch.empty(Mk, 2 * D, device=dev, dtype=torch.bfloat16)   # gradient of [k | v]
+        d_o = hip.sigmoid_gate_cols_bwd(dog, o, qg[:, D:], dqg[:, D:])
+        dqn, _, _ = hip.attention_cross_bwd(qn, kn, kv[:, D:], o, d_o, lse2, B, Lq, Lk, H, dk=dkv[:, :D], dv=dkv[:, D:])
+        _, dqn_w = hip.head_rmsnorm_bwd(dqn, qg[:, :D], qn_w, eps, H, dx=dqg[:, :D])
+        _, dkn_w = hip.head_rmsnorm_bwd(dkv[:, :D], kv[:, :D], kn_w, eps, H, dx=dkv[:, :D])      # in place
+        dxn = hip.gemm_nt(dqg, wqg_t, hip.EPI_BF16)
+        dcn = hip.gemm_nt(dkv, wkv_t, hip.EPI_BF16)
+        dwq = dwg = dwkv = dwo = None
+        jobs = []
+        if need[4] or need[6]:
+            dwqg = torch.empty(2 * D, D, device=dev)
+            dqg_, xn_ = _rows64(dqg, xn)
+            jobs.append(dict(A=dqg_, B=xn_, out=dwqg))
+        if need[5]:
+            dwkv = torch.empty(2 * D, Dc, device=dev)
+            dkv_, cn_ = _rows64(dkv, cn)
+            jobs.append(dict(A=dkv_, B=cn_, out=dwkv))
+        if need[9]:
+            dwo = torch.empty(D, D, device=dev)
+            gb_, og_ = _rows64(gb, og)
+            jobs.append(dict(A=gb_, B=og_, out=dwo))
+        if jobs:
+            hip.gemm_tn_grouped(jobs)
+        if need[4]:
+            dwq = dwqg[:D].contiguous()
+        if need[6]:
+            dwg = dwqg[D:].contiguous()
+        dx, _, dnq_w = hip.rmsnorm_any_bwd(dxn, x2, nq_w, rstd_x)
+        dc, _, dnkv_w = hip.rmsnorm_any_bwd(dcn, c2, nkv_w, rstd_c)
+        return (dx.reshape(B, Lq, D) if need[0] else None, dc.reshape(B, Lk, Dc) if need[1] else None, dnq_w if need[2] else None,
+                dnkv_w if need[3] else None, dwq, dwkv, dwg, dqn_w if need[7] else None, dkn_w if need[8] else None, dwo, None, None, None, None, None)

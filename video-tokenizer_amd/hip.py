@@ -68,6 +68,9 @@ SIGNATURES = {
     "vt_attention_causal_bwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "vt_attention_fwd_rows": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "vt_attention_bwd_rows": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "vt_attention_cross_fwd": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "vt_attention_cross_bwd": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i64,
+                                       c_vp, c_i64, c_vp, c_i64, c_vp, c_vp]),
     "vt_vq_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32]),
     "vt_vq_forward": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_f32, c_f32, c_f32, c_u64, c_vp, c_vp,
                               c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
@@ -95,12 +98,20 @@ SIGNATURES = {
     "vt_rope_rotate": (c_i32, [c_vp, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp]),
     "vt_sigmoid_gate_fwd": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_vp]),
     "vt_sigmoid_gate_bwd": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp]),
+    "vt_sigmoid_gate_cols_fwd": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_i32, c_vp, c_vp]),
+    "vt_sigmoid_gate_cols_bwd": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_vp, c_vp, c_i64, c_vp]),
     "vt_geglu_fwd": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i64, c_vp]),
     "vt_geglu_bwd": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i32, c_vp, c_vp]),
     "vt_scale_rows": (c_i32, [c_vp, c_f32, c_i64, c_i32, c_vp, c_vp, c_vp]),
     "vt_rmsnorm_fwd": (c_i32, [c_vp, c_vp, c_f32, c_i64, c_i32, c_vp, c_vp, c_vp]),
     "vt_rmsnorm_bwd_workspace_bytes": (c_sz, [c_i32]),
     "vt_rmsnorm_bwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "vt_rmsnorm_any_fwd": (c_i32, [c_vp, c_vp, c_f32, c_i64, c_i32, c_vp, c_vp, c_vp]),
+    "vt_rmsnorm_any_bwd_workspace_bytes": (c_sz, [c_i32]),
+    "vt_rmsnorm_any_bwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "vt_head_rmsnorm_fwd": (c_i32, [c_vp, c_i64, c_vp, c_f32, c_i64, c_i32, c_vp, c_i64, c_vp]),
+    "vt_head_rmsnorm_bwd_workspace_bytes": (c_sz, []),
+    "vt_head_rmsnorm_bwd": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_f32, c_i64, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp]),
     "vt_swiglu_fwd": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp]),
     "vt_swiglu_bwd": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_vp]),
     "vt_decode_attention": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i64, c_i32, c_vp, c_vp]),
@@ -464,6 +475,112 @@ def attention_causal_bwd(qkv, o, dO, lse2, B, L, H):
     delta = torch.zeros(B, H, L, device=qkv.device, dtype=torch.float32)
     check(lib().vt_attention_causal_bwd(ptr(qkv), ptr(o), ptr(dO), ptr(lse2), B, L, H, ptr(dqkv), ptr(delta), stream()), "vt_attention_causal_bwd")
     return dqkv
+
+
+def _rows_view(t, what):
+    """a bf16 matrix view with unit column stride (rows of a wider buffer allowed) -> its row stride in elements"""
+    if t.dtype != torch.bfloat16 or t.dim() != 2 or t.stride(1) != 1:
+        raise HipError(f"{what}: expected a 2-D bf16 view with unit column stride, got {t.dtype} {tuple(t.shape)} strides {tuple(t.stride())}")
+    return t.stride(0)
+
+
+def attention_cross_fwd(q, k, v, B, Lq, Lk, H, hd=64):
+    """softmax(q k^T / 8) v with the queries and the keys / values in separate (strided) operands: q a view [B * Lq, 64 H] of any wider
+    bf16 buffer, k and v views [B * Lk, 64 H] likewise -> (o bf16 [B * Lq, 64 H], lse2 fp32 [B, H, Lq])"""
+    require_gpu(q, k, v)
+    D = H * hd
+    assert tuple(q.shape) == (B * Lq, D) and tuple(k.shape) == (B * Lk, D) == tuple(v.shape)
+    o = torch.empty(B * Lq, D, device=q.device, dtype=torch.bfloat16)
+    lse2 = torch.empty(B, H, Lq, device=q.device, dtype=torch.float32)
+    check(lib().vt_attention_cross_fwd(ptr(q), _rows_view(q, "q"), ptr(k), _rows_view(k, "k"), ptr(v), _rows_view(v, "v"), B, Lq, Lk, H, hd,
+                                       ptr(o), ptr(lse2), stream()), "vt_attention_cross_fwd")
+    return o, lse2
+
+
+def attention_cross_bwd(q, k, v, o, dO, lse2, B, Lq, Lk, H, hd=64, dq=None, dk=None, dv=None):
+    """-> (dq, dk, dv); each may be passed as a view [rows, 64 H] of a wider bf16 buffer, whose other columns are left alone"""
+    require_gpu(q, k, v, o, dO, lse2, dq, dk, dv)
+    D = H * hd
+    assert tuple(q.shape) == (B * Lq, D) and tuple(k.shape) == (B * Lk, D) == tuple(v.shape)
+    assert o.is_contiguous() and dO.is_contiguous() and tuple(o.shape) == (B * Lq, D) == tuple(dO.shape)
+    dq = torch.empty(B * Lq, D, device=q.device, dtype=torch.bfloat16) if dq is None else dq
+    dk = torch.empty(B * Lk, D, device=q.device, dtype=torch.bfloat16) if dk is None else dk
+    dv = torch.empty(B * Lk, D, device=q.device, dtype=torch.bfloat16) if dv is None else dv
+    assert tuple(dq.shape) == (B * Lq, D) and tuple(dk.shape) == (B * Lk, D) == tuple(dv.shape)
+    delta = torch.empty(B, H, Lq, device=q.device, dtype=torch.float32)
+    check(lib().vt_attention_cross_bwd(ptr(q), _rows_view(q, "q"), ptr(k), _rows_view(k, "k"), ptr(v), _rows_view(v, "v"), ptr(o), ptr(dO), ptr(lse2),
+                                       B, Lq, Lk, H, hd, ptr(dq), _rows_view(dq, "dq"), ptr(dk), _rows_view(dk, "dk"), ptr(dv), _rows_view(dv, "dv"),
+                                       ptr(delta), stream()), "vt_attention_cross_bwd")
+    return dq, dk, dv
+
+
+def head_rmsnorm_fwd(x, w, eps, H):
+    """RMSNorm over each 64-element head vector: x a bf16 view [M, 64 H] (rows of a wider buffer allowed), w fp32 [64] -> y bf16 [M, 64 H]"""
+    require_gpu(x, w)
+    M = x.shape[0]
+    assert x.shape[1] == 64 * H and w.dtype == torch.float32 and w.numel() == 64 and w.is_contiguous()
+    y = torch.empty(M, 64 * H, device=x.device, dtype=torch.bfloat16)
+    check(lib().vt_head_rmsnorm_fwd(ptr(x), _rows_view(x, "x"), ptr(w), eps, M, H, ptr(y), y.stride(0), stream()), "vt_head_rmsnorm_fwd")
+    return y
+
+
+def head_rmsnorm_bwd(dy, x, w, eps, H, dx=None):
+    """-> (dx, dw fp32 [64]); dx defaults to a new dense matrix and may be `dy` itself (in place) or a view of a wider buffer"""
+    require_gpu(dy, x, w, dx)
+    M = x.shape[0]
+    assert x.shape[1] == 64 * H and tuple(dy.shape) == tuple(x.shape) and w.dtype == torch.float32 and w.numel() == 64 and w.is_contiguous()
+    dx = torch.empty(M, 64 * H, device=x.device, dtype=torch.bfloat16) if dx is None else dx
+    assert tuple(dx.shape) == tuple(x.shape)
+    dw = torch.empty(64, device=x.device, dtype=torch.float32)
+    ws = _ws(lib().vt_head_rmsnorm_bwd_workspace_bytes(), x.device)
+    check(lib().vt_head_rmsnorm_bwd(ptr(dy), _rows_view(dy, "dy"), ptr(x), _rows_view(x, "x"), ptr(w), eps, M, H, ptr(dx), _rows_view(dx, "dx"),
+                                    ptr(dw), ptr(ws), stream()), "vt_head_rmsnorm_bwd")
+    return dx, dw
+
+
+def sigmoid_gate_cols_fwd(o, gate):
+    """og = o * sigmoid(gate): o bf16 [M, D] dense, gate a bf16 view [M, D] of any wider buffer"""
+    require_gpu(o, gate)
+    M, D = o.shape
+    assert o.is_contiguous() and o.dtype == torch.bfloat16 and tuple(gate.shape) == (M, D)
+    og = torch.empty_like(o)
+    check(lib().vt_sigmoid_gate_cols_fwd(ptr(o), ptr(gate), _rows_view(gate, "gate"), M, D, ptr(og), stream()), "vt_sigmoid_gate_cols_fwd")
+    return og
+
+
+def sigmoid_gate_cols_bwd(dog, o, gate, dgate):
+    """returns d_o; writes the gate's gradient into the view `dgate` [M, D] (other columns of its buffer are left alone)"""
+    require_gpu(dog, o, gate, dgate)
+    M, D = o.shape
+    assert dog.is_contiguous() and o.is_contiguous() and dog.shape == o.shape and tuple(gate.shape) == (M, D) == tuple(dgate.shape)
+    d_o = torch.empty_like(o)
+    check(lib().vt_sigmoid_gate_cols_bwd(ptr(dog), ptr(o), ptr(gate), _rows_view(gate, "gate"), M, D, ptr(d_o), ptr(dgate), _rows_view(dgate, "dgate"),
+                                         stream()), "vt_sigmoid_gate_cols_bwd")
+    return d_o
+
+
+def rmsnorm_any_fwd(x, w, eps):
+    """vt_rmsnorm_fwd at the widths of model_design as well (128, 256, 512)"""
+    require_gpu(x, w)
+    rows, dim = x.shape
+    assert x.dtype == torch.float32 and x.is_contiguous() and w.dtype == torch.float32 and w.is_contiguous()
+    y = torch.empty(rows, dim, device=x.device, dtype=torch.bfloat16)
+    rstd = torch.empty(rows, device=x.device, dtype=torch.float32)
+    check(lib().vt_rmsnorm_any_fwd(ptr(x), ptr(w), eps, rows, dim, ptr(y), ptr(rstd), stream()), "vt_rmsnorm_any_fwd")
+    return y, rstd
+
+
+def rmsnorm_any_bwd(dy, x, w, rstd, dres=None, want_bf16=False):
+    require_gpu(dy, x, w, rstd, dres)
+    rows, dim = x.shape
+    assert dy.is_contiguous() and dy.dtype == torch.bfloat16 and tuple(dy.shape) == (rows, dim)
+    dx = torch.empty_like(x)
+    dxb = torch.empty(rows, dim, device=x.device, dtype=torch.bfloat16) if want_bf16 else None
+    dw = torch.empty(dim, device=x.device, dtype=torch.float32)
+    ws = _ws(lib().vt_rmsnorm_any_bwd_workspace_bytes(dim), x.device)
+    check(lib().vt_rmsnorm_any_bwd(ptr(dy), ptr(x), ptr(w), ptr(rstd), ptr(dres), rows, dim, ptr(dx), ptr(dxb), ptr(dw), ptr(ws), stream()),
+          "vt_rmsnorm_any_bwd")
+    return dx, dxb, dw
 
 
 def rmsnorm_fwd(x, w, eps):
