@@ -409,6 +409,39 @@ int vt_head_rmsnorm_fwd(const void* x, int64_t x_rs, const float* w, float eps, 
 size_t vt_head_rmsnorm_bwd_workspace_bytes(void);
 int vt_head_rmsnorm_bwd(const void* dy, int64_t dy_rs, const void* x, int64_t x_rs, const float* w, float eps, int64_t M, int32_t H, void* dx,
                         int64_t dx_rs, float* dw, void* workspace, vtStream stream);
+/* Row passes of model_design's self-attention block and stack (models/model_design/base/transformer.py:46-85, 148-216; csrc/vt_design.hip).
+ *   vt_qkrms_rope_fwd: the RMS twin of vt_qknorm_rope_fwd.  qkvg bf16 [M, >= 3D] (row stride in_rs; the block passes the [M, 4D] output of one
+ *     GEMM on [to_qkv ; to_gate], columns q | k | v | gate) -> qkv_out bf16 [M, 3D] (row stride out_rs), the packed operand of vt_attention_fwd:
+ *     q and k per head t = bf16(bf16(x rstd) w), rstd = rsqrt(mean(x^2) + eps) in fp32 (vt_head_rmsnorm_fwd), then the rotation of
+ *     vt_rope_rotate (row m has position m % L, tables fp32 [L, 32]); v copied.  Bit for bit that chain of three passes.  D = 64 H, M = B L;
+ *     row strides >= 3D and multiples of 8, buffers 16-byte aligned.  Columns past 3D and rows past M are neither read nor written.
+ *   vt_qkrms_rope_bwd: dqkv bf16 [M, 3D] dense (from vt_attention_bwd) -> columns 0..3D of dqkvg (row stride out_rs): dq, dk rotated by the
+ *     conjugate and rounded to bf16, then the backward of vt_head_rmsnorm_bwd with rstd recomputed from qkvg; dv copied.  dq_w / dk_w fp32 [64]
+ *     (either may be NULL) from 512 per-workgroup partials in `workspace` (vt_qkrms_rope_bwd_workspace_bytes()) that a second launch sums in a
+ *     fixed order.  Not in place.
+ *   vt_residual_scale_fwd: out = x + float(bf16(s y)), the residual `x + res_scale * f(x)` (:176-183) with s = *scale_dev a 0-dim parameter
+ *     in DEVICE memory (no host read: capturable).  x, y, out fp32 [rows, dim], y holding bf16 values; torch forms the product in bf16 (s is
+ *     converted to bf16, the fp32 product rounded once) and adds the fp32 x after.  dim % 4 == 0, any rows, 16-byte aligned, not in place.
+ *   vt_residual_scale_bwd: g = bf16(dout); dy = float(bf16(s g)); *dscale = sum g y in fp32 from at most 256 per-workgroup partials in
+ *     `workspace` (vt_residual_scale_bwd_workspace_bytes()) summed in a fixed order by a second launch: bit-identical run to run.  dscale NULL
+ *     (a frozen scale): y and workspace may be NULL too.
+ *   vt_rmsnorm_any_f32_fwd / _bwd: vt_rmsnorm_any_* with an fp32, unrounded output y = x rstd w and an fp32 incoming gradient (final_norm of the
+ *     stack, :211-216: the reference's RMSNorm on an fp32 input returns fp32).  Same widths, dw from fixed-order partials
+ *     (vt_rmsnorm_any_f32_bwd_workspace_bytes(dim)). */
+int vt_qkrms_rope_fwd(const void* qkvg, int64_t in_rs, int64_t M, int32_t L, int32_t H, const float* q_w, const float* k_w, float eps,
+                      const float* cos_tab, const float* sin_tab, void* qkv_out, int64_t out_rs, vtStream stream);
+size_t vt_qkrms_rope_bwd_workspace_bytes(void);
+int vt_qkrms_rope_bwd(const void* qkvg, int64_t in_rs, const void* dqkv, int64_t M, int32_t L, int32_t H, const float* q_w, const float* k_w,
+                      float eps, const float* cos_tab, const float* sin_tab, void* dqkvg, int64_t out_rs, float* dq_w, float* dk_w,
+                      void* workspace, vtStream stream);
+int vt_residual_scale_fwd(const float* x, const float* y, const float* scale_dev, int64_t rows, int32_t dim, float* out, vtStream stream);
+size_t vt_residual_scale_bwd_workspace_bytes(void);
+int vt_residual_scale_bwd(const float* dout, const float* y, const float* scale_dev, int64_t rows, int32_t dim, float* dy, float* dscale,
+                          void* workspace, vtStream stream);
+int vt_rmsnorm_any_f32_fwd(const float* x, const float* w, float eps, int64_t rows, int32_t dim, float* y, float* rstd, vtStream stream);
+size_t vt_rmsnorm_any_f32_bwd_workspace_bytes(int32_t dim);
+int vt_rmsnorm_any_f32_bwd(const float* dy, const float* x, const float* w, const float* rstd, int64_t rows, int32_t dim, float* dx, float* dw,
+                           void* workspace, vtStream stream);
 int vt_swiglu_fwd(const void* h, int64_t M, int32_t I, void* a, vtStream stream);
 int vt_swiglu_bwd(const void* da, const void* h, int64_t M, int32_t I, void* dh, vtStream stream);
 int vt_decode_attention(const void* q, const void* k_cache, const void* v_cache, int32_t B, int32_t H, int64_t Lmax, int32_t n_keys, void* o,

@@ -10,6 +10,10 @@ only owns the tensors, the autograd graph and a few O(B x D) glue ops.
 Mixed-precision contract = the engine's: fp32 residual stream and LayerNorm statistics,
 bf16 MFMA operands with fp32 accumulation, Linear outputs rounded to bf16 where autocast would.
 No CPU path: CPU tensors are refused by hip.ptr().
+
+The layers of the reference's `autoencoder_design` are here as well: CrossAttentionLayer, and the self-attention block of its stack
+(SelfAttentionLayer, FeedForwardLayer, ResidualScale with the learnable 0-dim residual scale read on the device, RMSNormF32 for the stack's
+fp32 final norm); design.py holds their parameters.
 """
 import ctypes
 
@@ -523,3 +527,187 @@ class CrossAttentionLayer(torch.autograd.Function):
         dc, _, dnkv_w = hip.rmsnorm_any_bwd(dcn, c2, nkv_w, rstd_c)
         return (dx.reshape(B, Lq, D) if need[0] else None, dc.reshape(B, Lk, Dc) if need[1] else None, dnq_w if need[2] else None,
                 dnkv_w if need[3] else None, dwq, dwkv, dwg, dqn_w if need[7] else None, dkn_w if need[8] else None, dwo, None, None, None, None, None)
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# model_design's self-attention block and stack (models/model_design/base/transformer.py:30-85, 148-216)
+# ------------------------------------------------------------------------------------------------------------------------
+class ResidualScale(torch.autograd.Function):
+    """x + res_scale * y (transformer.py:176-183) on vt_residual_scale_*: x fp32 [..., D], y fp32 of the same shape holding the bf16 values
+    a layer returned, res_scale a 0-dim fp32 parameter read on the device.  torch forms res_scale * y in bf16 (the scale converted to bf16, one
+    rounding of the product) and adds the fp32 x after; the gradient of the scale is the fp32 sum of bf16(dout) * y in a fixed order."""
+
+    @staticmethod
+    def forward(ctx, x, y, scale):
+        hip.require_gpu(x, y, scale)
+        D = x.shape[-1]
+        x2 = x.contiguous().reshape(-1, D).float()
+        y2 = y.contiguous().reshape(-1, D).float()
+        s = scale.detach().float()
+        out = hip.residual_scale_fwd(x2, y2, s)
+        ctx.save_for_backward(y2, s)
+        return out.reshape(x.shape)
+
+    @staticmethod
+    def backward(ctx, dout):
+        y2, s = ctx.saved_tensors
+        d2 = dout.contiguous().reshape(y2.shape).float()
+        dy, ds = hip.residual_scale_bwd(d2, y2, s, want_ds=ctx.needs_input_grad[2])
+        return dout, dy.reshape(dout.shape) if ctx.needs_input_grad[1] else None, ds
+
+
+class RMSNormRows(torch.autograd.Function):
+    """RMSNorm (transformer.py:18-27) of rows that a bf16 Linear reads next, on vt_rmsnorm_any_*: fp32 in, the bf16-rounded output returned in
+    an fp32 tensor (cond_adapter.0 of the design's decoder)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, eps):
+        hip.require_gpu(x, weight)
+        x2 = x.contiguous().reshape(-1, x.shape[-1]).float()
+        w = weight.detach().float().contiguous()
+        y, rstd = hip.rmsnorm_any_fwd(x2, w, eps)
+        ctx.save_for_backward(x2, w, rstd)
+        return y.float().reshape(x.shape)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x2, w, rstd = ctx.saved_tensors
+        dx, _, dw = hip.rmsnorm_any_bwd(hip.cast_rows(dy.contiguous().reshape(x2.shape).float()), x2, w, rstd)
+        return dx.reshape(dy.shape), dw if ctx.needs_input_grad[1] else None, None
+
+
+class RMSNormF32(torch.autograd.Function):
+    """final_norm of the stack (transformer.py:211, 216): RMSNorm of the fp32 residual stream with an fp32, unrounded output (vt_rmsnorm_any_f32_*)"""
+
+    @staticmethod
+    def forward(ctx, x, weight, eps):
+        hip.require_gpu(x, weight)
+        x2 = x.contiguous().reshape(-1, x.shape[-1]).float()
+        w = weight.detach().float().contiguous()
+        y, rstd = hip.rmsnorm_any_f32_fwd(x2, w, eps)
+        ctx.save_for_backward(x2, w, rstd)
+        return y.reshape(x.shape)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x2, w, rstd = ctx.saved_tensors
+        dx, dw = hip.rmsnorm_any_f32_bwd(dy.contiguous().reshape(x2.shape).float(), x2, w, rstd)
+        return dx.reshape(dy.shape), dw if ctx.needs_input_grad[1] else None, None
+
+
+class SelfAttentionLayer(torch.autograd.Function):
+    """x + res_scale * SelfAttention(x) (transformer.py:67-85, 176) on x fp32 [B, L, D], D = 64 H, as seven launches: rmsnorm_any(x); ONE GEMM on
+    [to_qkv ; to_gate] (N = 4D, columns q | k | v | gate); vt_qkrms_rope_fwd (head RMSNorm and rotation of q and k, v copied, into the packed
+    attention operand); vt_attention_fwd; the gate from columns 3D..4D; out_proj; vt_residual_scale_fwd.  Rounding points of autocast(bf16):
+    bf16 Linear outputs, bf16 head norm, rotation, attention output and gate product, the residual product in bf16, fp32 x and dx.
+    pk_*: (bf16 [N, K], bf16 [K, N]) operand copies of [to_qkv ; to_gate] and out_proj (hip.pack_weight)."""
+
+    @staticmethod
+    def forward(ctx, x, cos, sin, res_scale, norm_w, to_qkv_w, to_gate_w, q_norm_w, k_norm_w, out_proj_w, H, eps, pk_qkvg, pk_o):
+        hip.require_gpu(x, cos, sin, res_scale, norm_w, to_qkv_w, to_gate_w, q_norm_w, k_norm_w, out_proj_w)
+        B, L, D = x.shape
+        assert D == 64 * H and to_qkv_w.shape == (3 * D, D) and cos.shape == (L, 32) == sin.shape
+        M = B * L
+        x2 = x.contiguous().reshape(M, D).float()
+        n_w, qn_w, kn_w, s = (t.detach().float().contiguous() for t in (norm_w, q_norm_w, k_norm_w, res_scale))
+        cos, sin = cos.contiguous(), sin.contiguous()
+        xn, rstd = hip.rmsnorm_any_fwd(x2, n_w, eps)
+        qkvg = hip.gemm_nt(xn, pk_qkvg[0], hip.EPI_BF16)                 # [M, 4D] = [q | k | v | gate]
+        qkv = hip.qkrms_rope_fwd(qkvg, L, H, qn_w, kn_w, eps, cos, sin)
+        o, lse2 = hip.attention_fwd(qkv, B, L, H)
+        og = hip.sigmoid_gate_fwd(o, qkvg)
+        y = hip.gemm_nt(og, pk_o[0], hip.EPI_F32, round_bf16=True)
+        out = hip.residual_scale_fwd(x2, y, s)
+        ctx.save_for_backward(x2, n_w, qn_w, kn_w, s, cos, sin, rstd, xn, qkvg, qkv, o, lse2, og, y, pk_qkvg[1], pk_o[1])
+        ctx.geom = (B, L, D, H, eps)
+        return out.reshape(B, L, D)
+
+    @staticmethod
+    def backward(ctx, dout):
+        x2, n_w, qn_w, kn_w, s, cos, sin, rstd, xn, qkvg, qkv, o, lse2, og, y, wqkvg_t, wo_t = ctx.saved_tensors
+        B, L, D, H, eps = ctx.geom
+        M = B * L
+        dev = dout.device
+        need = ctx.needs_input_grad
+        d2 = dout.contiguous().reshape(M, D).float()
+        dy, ds = hip.residual_scale_bwd(d2, y, s, want_ds=need[3])
+        gb = hip.cast_rows(dy)                                           # exact: dy holds bf16 values
+        dog = hip.gemm_nt(gb, wo_t, hip.EPI_BF16)
+        dqkvg = torch.empty(M, 4 * D, device=dev, dtype=torch.bfloat16)  # gradient of [q | k | v | gate], every column written below
+        d_o = hip.sigmoid_gate_bwd(dog, o, qkvg, dqkvg)
+        dqkv = hip.attention_bwd(qkv, o, d_o, lse2, B, L, H)
+        dqn_w, dkn_w = hip.qkrms_rope_bwd(qkvg, dqkv, L, H, qn_w, kn_w, eps, cos, sin, dqkvg, want_dw=need[7] or need[8])
+        dxn = hip.gemm_nt(dqkvg, wqkvg_t, hip.EPI_BF16)                  # the gradients from to_qkv and to_gate summed in fp32, rounded once
+        dwqkv = dwg = dwo = None
+        jobs = []
+        if need[5] or need[6]:
+            dwqkvg = torch.empty(4 * D, D, device=dev)
+            a_, b_ = _rows64(dqkvg, xn)
+            jobs.append(dict(A=a_, B=b_, out=dwqkvg))
+        if need[9]:
+            dwo = torch.empty(D, D, device=dev)
+            a_, b_ = _rows64(gb, og)
+            jobs.append(dict(A=a_, B=b_, out=dwo))
+        if jobs:
+            hip.gemm_tn_grouped(jobs)
+        if need[5]:
+            dwqkv = dwqkvg[:3 * D].contiguous()
+        if need[6]:
+            dwg = dwqkvg[3 * D:].contiguous()
+        dx, _, dn_w = hip.rmsnorm_any_bwd(dxn, x2, n_w, rstd, dres=d2)   # + the residual path's gradient
+        return (dx.reshape(B, L, D) if need[0] else None, None, None, ds, dn_w if need[4] else None, dwqkv, dwg, dqn_w if need[7] else None,
+                dkn_w if need[8] else None, dwo, None, None, None, None)
+
+
+class FeedForwardLayer(torch.autograd.Function):
+    """x + res_scale * ffn(x) with ffn = make_ffn (transformer.py:30-39, 183): rmsnorm_any(x); the fc1 GEMM (N = 2 inner); vt_geglu_fwd into an
+    operand whose row stride is padded to a multiple of 64 (inner is 1376 at width 512); the fc2 GEMM; vt_residual_scale_fwd.
+    pk_1: operand copies of ffn.1; pk_2: of ffn.3 with the contraction dim padded to that multiple (pack_weight(k_pad=))."""
+
+    @staticmethod
+    def forward(ctx, x, res_scale, norm_w, fc1_w, fc2_w, eps, pk_1, pk_2):
+        hip.require_gpu(x, res_scale, norm_w, fc1_w, fc2_w)
+        shp = x.shape
+        D = shp[-1]
+        inner = fc2_w.shape[1]
+        assert fc1_w.shape == (2 * inner, D) and fc2_w.shape[0] == D
+        x2 = x.contiguous().reshape(-1, D).float()
+        n_w, s = norm_w.detach().float().contiguous(), res_scale.detach().float()
+        xn, rstd = hip.rmsnorm_any_fwd(x2, n_w, eps)
+        h = hip.gemm_nt(xn, pk_1[0], hip.EPI_BF16)                      # [M, 2 inner] = [x | gate]
+        a = hip.geglu_fwd(h, lda=_pad64(inner))
+        y = hip.gemm_nt(a, pk_2[0], hip.EPI_F32, round_bf16=True)
+        out = hip.residual_scale_fwd(x2, y, s)
+        ctx.save_for_backward(x2, n_w, s, rstd, xn, h, a, y, pk_1[1], pk_2[1])
+        ctx.inner = inner
+        return out.reshape(shp)
+
+    @staticmethod
+    def backward(ctx, dout):
+        x2, n_w, s, rstd, xn, h, a, y, w1_t, w2_t = ctx.saved_tensors
+        M, D = x2.shape
+        inner = ctx.inner
+        dev = dout.device
+        need = ctx.needs_input_grad
+        d2 = dout.contiguous().reshape(M, D).float()
+        dy, ds = hip.residual_scale_bwd(d2, y, s, want_ds=need[1])
+        gb = hip.cast_rows(dy)
+        da = hip.gemm_nt(gb, w2_t, hip.EPI_BF16)                        # [M, pad64(inner)]
+        dh = hip.geglu_bwd(da, h)
+        dxn = hip.gemm_nt(dh, w1_t, hip.EPI_BF16)
+        dw1 = dw2 = None
+        jobs = []
+        if need[3]:
+            dw1 = torch.empty(2 * inner, D, device=dev)
+            a_, b_ = _rows64(dh, xn)
+            jobs.append(dict(A=a_, B=b_, out=dw1))
+        if need[4]:
+            dw2p = torch.empty(D, a.shape[1], device=dev)
+            a_, b_ = _rows64(gb, a)
+            jobs.append(dict(A=a_, B=b_, out=dw2p))
+        if jobs:
+            hip.gemm_tn_grouped(jobs)
+        if need[4]:
+            dw2 = dw2p[:, :inner].contiguous()
+        dx, _, dn_w = hip.rmsnorm_any_bwd(dxn, x2, n_w, rstd, dres=d2)
+        return dx.reshape(dout.shape) if need[0] else None, ds, dn_w if need[2] else None, dw1, dw2, None, None, None

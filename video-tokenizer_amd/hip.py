@@ -112,6 +112,15 @@ SIGNATURES = {
     "vt_head_rmsnorm_fwd": (c_i32, [c_vp, c_i64, c_vp, c_f32, c_i64, c_i32, c_vp, c_i64, c_vp]),
     "vt_head_rmsnorm_bwd_workspace_bytes": (c_sz, []),
     "vt_head_rmsnorm_bwd": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_f32, c_i64, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "vt_qkrms_rope_fwd": (c_i32, [c_vp, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "vt_qkrms_rope_bwd_workspace_bytes": (c_sz, []),
+    "vt_qkrms_rope_bwd": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "vt_residual_scale_fwd": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_vp]),
+    "vt_residual_scale_bwd_workspace_bytes": (c_sz, []),
+    "vt_residual_scale_bwd": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "vt_rmsnorm_any_f32_fwd": (c_i32, [c_vp, c_vp, c_f32, c_i64, c_i32, c_vp, c_vp, c_vp]),
+    "vt_rmsnorm_any_f32_bwd_workspace_bytes": (c_sz, [c_i32]),
+    "vt_rmsnorm_any_f32_bwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "vt_swiglu_fwd": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp]),
     "vt_swiglu_bwd": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_vp]),
     "vt_decode_attention": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i64, c_i32, c_vp, c_vp]),
@@ -888,3 +897,82 @@ def geglu_bwd(da, h):
     dh = torch.empty_like(h)
     check(lib().vt_geglu_bwd(ptr(da), da.shape[1], ptr(h), M, I2 // 2, ptr(dh), stream()), "vt_geglu_bwd")
     return dh
+
+
+# ---- row passes of model_design's self-attention block and stack (csrc/vt_design.hip) ----
+def _tables_ok(cos, sin, L):
+    return cos.dtype == torch.float32 and sin.dtype == torch.float32 and cos.is_contiguous() and sin.is_contiguous() and cos.shape == (L, 32) == sin.shape
+
+
+def qkrms_rope_fwd(qkvg, L, H, q_w, k_w, eps, cos, sin, rows=None, out=None):
+    """qkvg a bf16 view [>= M, >= 3 * 64 H] (rows of the wider [M, 4D] projection) -> packed bf16 [M, 3 * 64 H]: q, k RMS-normalised per head
+    and rotated, v copied; the first `rows` rows (default all)"""
+    require_gpu(qkvg, q_w, k_w, cos, sin, out)
+    M = qkvg.shape[0] if rows is None else rows
+    assert qkvg.dtype == torch.bfloat16 and qkvg.dim() == 2 and qkvg.shape[1] >= 3 * 64 * H and 0 < M <= qkvg.shape[0] and _tables_ok(cos, sin, L)
+    assert q_w.dtype == torch.float32 and k_w.dtype == torch.float32 and q_w.numel() == 64 == k_w.numel() and q_w.is_contiguous() and k_w.is_contiguous()
+    out = torch.empty(M, 3 * 64 * H, device=qkvg.device, dtype=torch.bfloat16) if out is None else out
+    assert out.dtype == torch.bfloat16 and out.shape[0] >= M and out.shape[1] >= 3 * 64 * H
+    check(lib().vt_qkrms_rope_fwd(ptr(qkvg), _rows_view(qkvg, "qkvg"), M, L, H, ptr(q_w), ptr(k_w), eps, ptr(cos), ptr(sin), ptr(out),
+                                  _rows_view(out, "out"), stream()), "vt_qkrms_rope_fwd")
+    return out
+
+
+def qkrms_rope_bwd(qkvg, dqkv, L, H, q_w, k_w, eps, cos, sin, dqkvg, want_dw=True):
+    """writes columns 0..3D of the bf16 view dqkvg in place; returns (dq_w, dk_w) fp32 [64] each, or (None, None)"""
+    require_gpu(qkvg, dqkv, dqkvg, q_w, k_w, cos, sin)
+    M = dqkv.shape[0]
+    assert dqkv.dtype == torch.bfloat16 and dqkv.is_contiguous() and dqkv.shape == (M, 3 * 64 * H) and qkvg.shape[0] >= M and dqkvg.shape[0] >= M
+    assert qkvg.dtype == torch.bfloat16 and dqkvg.dtype == torch.bfloat16 and qkvg.shape[1] >= 3 * 64 * H and dqkvg.shape[1] >= 3 * 64 * H and _tables_ok(cos, sin, L)
+    dw = torch.empty(2, 64, device=qkvg.device) if want_dw else None
+    ws = _ws(lib().vt_qkrms_rope_bwd_workspace_bytes(), qkvg.device)
+    check(lib().vt_qkrms_rope_bwd(ptr(qkvg), _rows_view(qkvg, "qkvg"), ptr(dqkv), M, L, H, ptr(q_w), ptr(k_w), eps, ptr(cos), ptr(sin), ptr(dqkvg),
+                                  _rows_view(dqkvg, "dqkvg"), ptr(dw[0]) if want_dw else None, ptr(dw[1]) if want_dw else None, ptr(ws), stream()),
+          "vt_qkrms_rope_bwd")
+    return (dw[0], dw[1]) if want_dw else (None, None)
+
+
+def residual_scale_fwd(x, y, scale):
+    """x + float(bf16(scale * y)): x, y fp32 [rows, dim] (y holding bf16 values), scale a 0-dim fp32 DEVICE tensor"""
+    require_gpu(x, y, scale)
+    assert x.dtype == torch.float32 and y.dtype == torch.float32 and x.is_contiguous() and y.is_contiguous() and x.shape == y.shape and x.dim() == 2
+    assert scale.dtype == torch.float32 and scale.numel() == 1
+    out = torch.empty_like(x)
+    check(lib().vt_residual_scale_fwd(ptr(x), ptr(y), ptr(scale), x.shape[0], x.shape[1], ptr(out), stream()), "vt_residual_scale_fwd")
+    return out
+
+
+def residual_scale_bwd(dout, y, scale, want_ds=True):
+    """-> (dy fp32 holding bf16 values, dscale 0-dim fp32 or None)"""
+    require_gpu(dout, y, scale)
+    assert dout.dtype == torch.float32 and dout.is_contiguous() and dout.dim() == 2 and scale.dtype == torch.float32 and scale.numel() == 1
+    assert y is None or (y.dtype == torch.float32 and y.is_contiguous() and y.shape == dout.shape)
+    dy = torch.empty_like(dout)
+    ds = torch.empty((), device=dout.device, dtype=torch.float32) if want_ds else None
+    ws = _ws(lib().vt_residual_scale_bwd_workspace_bytes(), dout.device) if want_ds else None
+    check(lib().vt_residual_scale_bwd(ptr(dout), ptr(y), ptr(scale), dout.shape[0], dout.shape[1], ptr(dy), ptr(ds), ptr(ws), stream()),
+          "vt_residual_scale_bwd")
+    return dy, ds
+
+
+def rmsnorm_any_f32_fwd(x, w, eps):
+    """RMSNorm with an fp32, unrounded output (final_norm of model_design's stack): -> (y fp32, rstd fp32 [rows])"""
+    require_gpu(x, w)
+    rows, dim = x.shape
+    assert x.dtype == torch.float32 and x.is_contiguous() and w.dtype == torch.float32 and w.is_contiguous()
+    y = torch.empty_like(x)
+    rstd = torch.empty(rows, device=x.device, dtype=torch.float32)
+    check(lib().vt_rmsnorm_any_f32_fwd(ptr(x), ptr(w), eps, rows, dim, ptr(y), ptr(rstd), stream()), "vt_rmsnorm_any_f32_fwd")
+    return y, rstd
+
+
+def rmsnorm_any_f32_bwd(dy, x, w, rstd):
+    """dy fp32 -> (dx fp32, dw fp32 [dim])"""
+    require_gpu(dy, x, w, rstd)
+    rows, dim = x.shape
+    assert dy.dtype == torch.float32 and dy.is_contiguous() and tuple(dy.shape) == (rows, dim)
+    dx = torch.empty_like(x)
+    dw = torch.empty(dim, device=x.device, dtype=torch.float32)
+    ws = _ws(lib().vt_rmsnorm_any_f32_bwd_workspace_bytes(dim), x.device)
+    check(lib().vt_rmsnorm_any_f32_bwd(ptr(dy), ptr(x), ptr(w), ptr(rstd), rows, dim, ptr(dx), ptr(dw), ptr(ws), stream()), "vt_rmsnorm_any_f32_bwd")
+    return dx, dw
