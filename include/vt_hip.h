@@ -381,6 +381,7 @@ int vt_scale_rows(const float* src, float scale, int64_t rows, int32_t dim, floa
  *   vt_rmsnorm_fwd / _bwd: RMSNorm (models/norm.py:6-17) y = x * rsqrt(mean(x^2) + eps) * w, x fp32 [rows, dim], y bf16, rstd fp32
  *     [rows] saved; backward adds `dres` (may be NULL), writes dx fp32 and/or bf16 and dw [dim] (fixed-order partial sums in
  *     `workspace` of vt_rmsnorm_bwd_workspace_bytes(dim)).  dim in {384, 768, 1024, 1280, 1536, 2560} (the llama-abs sizes).
+ *     csrc/vt_rmsnorm.hip, with the two other RMSNorm families below: one pair of kernel templates, one dispatch.
  *   vt_swiglu_fwd / _bwd: FeedForward (larp_ar.py:122-136) a = silu(w1 x) * (w3 x) on the packed projection h [M, 2I] = [w3 x | w1 x].
  *   vt_decode_attention: one new token per sequence against the KV cache (larp_ar.py:138-190, `mask = causal_mask[:, None, pos]`):
  *     q bf16 [B, H, 64], caches bf16 [>=B, H, Lmax, 64], keys 0..n_keys-1 -> o bf16 [B, H, 64].
@@ -393,7 +394,7 @@ int vt_rmsnorm_fwd(const float* x, const float* w, float eps, int64_t rows, int3
 size_t vt_rmsnorm_bwd_workspace_bytes(int32_t dim);
 int vt_rmsnorm_bwd(const void* dy_bf16, const float* x, const float* w, const float* rstd, const float* dres, int64_t rows, int32_t dim,
                    float* dx, void* dx_bf16, float* dw, void* workspace, vtStream stream);
-/* vt_rmsnorm_any_*: the same kernels, additionally at the widths 128, 256 and 512 of model_design (its 'small' is 512 wide, which
+/* vt_rmsnorm_any_*: the same kernels (csrc/vt_rmsnorm.hip), additionally at the widths 128, 256 and 512 of model_design (its 'small' is 512 wide, which
  * vt_rmsnorm_* refuses); bit-equal to vt_rmsnorm_* at the widths both accept. */
 int vt_rmsnorm_any_fwd(const float* x, const float* w, float eps, int64_t rows, int32_t dim, void* y_bf16, float* rstd, vtStream stream);
 size_t vt_rmsnorm_any_bwd_workspace_bytes(int32_t dim);
@@ -409,14 +410,15 @@ int vt_head_rmsnorm_fwd(const void* x, int64_t x_rs, const float* w, float eps, 
 size_t vt_head_rmsnorm_bwd_workspace_bytes(void);
 int vt_head_rmsnorm_bwd(const void* dy, int64_t dy_rs, const void* x, int64_t x_rs, const float* w, float eps, int64_t M, int32_t H, void* dx,
                         int64_t dx_rs, float* dw, void* workspace, vtStream stream);
-/* Row passes of model_design's self-attention block and stack (models/model_design/base/transformer.py:46-85, 148-216; csrc/vt_design.hip).
+/* Row passes of model_design's self-attention block and stack (models/model_design/base/transformer.py:46-85, 148-216; csrc/vt_design.hip,
+ * the final norm csrc/vt_rmsnorm.hip).
  *   vt_qkrms_rope_fwd: the RMS twin of vt_qknorm_rope_fwd.  qkvg bf16 [M, >= 3D] (row stride in_rs; the block passes the [M, 4D] output of one
  *     GEMM on [to_qkv ; to_gate], columns q | k | v | gate) -> qkv_out bf16 [M, 3D] (row stride out_rs), the packed operand of vt_attention_fwd:
  *     q and k per head t = bf16(bf16(x rstd) w), rstd = rsqrt(mean(x^2) + eps) in fp32 (vt_head_rmsnorm_fwd), then the rotation of
  *     vt_rope_rotate (row m has position m % L, tables fp32 [L, 32]); v copied.  Bit for bit that chain of three passes.  D = 64 H, M = B L;
  *     row strides >= 3D and multiples of 8, buffers 16-byte aligned.  Columns past 3D and rows past M are neither read nor written.
  *   vt_qkrms_rope_bwd: dqkv bf16 [M, 3D] dense (from vt_attention_bwd) -> columns 0..3D of dqkvg (row stride out_rs): dq, dk rotated by the
- *     conjugate and rounded to bf16, then the backward of vt_head_rmsnorm_bwd with rstd recomputed from qkvg; dv copied.  dq_w / dk_w fp32 [64]
+ *     conjugate and rounded to bf16, then the backward of vt_head_rmsnorm_bwd (the same device functions, csrc/vt_headvec.h) with rstd recomputed from qkvg; dv copied.  dq_w / dk_w fp32 [64]
  *     (either may be NULL) from 512 per-workgroup partials in `workspace` (vt_qkrms_rope_bwd_workspace_bytes()) that a second launch sums in a
  *     fixed order.  Not in place.
  *   vt_residual_scale_fwd: out = x + float(bf16(s y)), the residual `x + res_scale * f(x)` (:176-183) with s = *scale_dev a 0-dim parameter
@@ -426,7 +428,8 @@ int vt_head_rmsnorm_bwd(const void* dy, int64_t dy_rs, const void* x, int64_t x_
  *     `workspace` (vt_residual_scale_bwd_workspace_bytes()) summed in a fixed order by a second launch: bit-identical run to run.  dscale NULL
  *     (a frozen scale): y and workspace may be NULL too.
  *   vt_rmsnorm_any_f32_fwd / _bwd: vt_rmsnorm_any_* with an fp32, unrounded output y = x rstd w and an fp32 incoming gradient (final_norm of the
- *     stack, :211-216: the reference's RMSNorm on an fp32 input returns fp32).  Same widths, dw from fixed-order partials
+ *     stack, :211-216: the reference's RMSNorm on an fp32 input returns fp32).  The same kernel templates with T = float, so rstd, dx and dw are
+ *     bit-equal to vt_rmsnorm_any_* on a gradient that bf16 represents exactly, and y differs by its rounding only.  Same widths, dw from fixed-order partials
  *     (vt_rmsnorm_any_f32_bwd_workspace_bytes(dim)). */
 int vt_qkrms_rope_fwd(const void* qkvg, int64_t in_rs, int64_t M, int32_t L, int32_t H, const float* q_w, const float* k_w, float eps,
                       const float* cos_tab, const float* sin_tab, void* qkv_out, int64_t out_rs, vtStream stream);

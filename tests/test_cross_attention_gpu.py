@@ -282,3 +282,20 @@ def test_rmsnorm_any_equals_rmsnorm_where_both_accept(hip, rows):
         hip.rmsnorm_any_fwd(torch.zeros(4, 192, device="cuda"), torch.ones(192, device="cuda"), 1e-5)
     with pytest.raises(hip.HipError, match="GPU tensors only"):
         hip.rmsnorm_any_fwd(torch.zeros(4, 512), torch.ones(512), 1e-5)
+
+
+@pytest.mark.parametrize("rows,dim", [(5, 128), (1029, 384), (8197, 128), (9, 2560)])
+def test_rmsnorm_any_f32_equals_rmsnorm_any_up_to_the_output_rounding(hip, rows, dim):
+    """the fp32 and the bf16 family are instances of one kernel template: the same statistics, the same products, and the only difference the
+    rounding of y.  5 rows: a partial block; 1029: one row past a full sweep of the backward's 256 x 4-row grid; 8197: one row past the
+    forward's 2048-block cap; 2560: the last width of the dispatch"""
+    x = torch.from_numpy(gen.normal((rows, dim), 54)).cuda() * 1.7
+    w = 1.0 + torch.from_numpy(gen.normal((dim,), 55, 0.2)).cuda()
+    dy = torch.from_numpy(gen.normal((rows, dim), 56)).cuda().to(torch.bfloat16)      # exactly representable in both families' input type
+    y, rstd = hip.rmsnorm_any_fwd(x, w, 1e-5)
+    y32, rstd32 = hip.rmsnorm_any_f32_fwd(x, w, 1e-5)
+    assert torch.equal(rstd32, rstd)
+    assert y32.dtype == torch.float32 and torch.equal(y32.to(torch.bfloat16), y)
+    dx, _, dw = hip.rmsnorm_any_bwd(dy, x, w, rstd)
+    dx32, dw32 = hip.rmsnorm_any_f32_bwd(dy.float(), x, w, rstd)
+    assert torch.equal(dx32, dx) and torch.equal(dw32, dw)

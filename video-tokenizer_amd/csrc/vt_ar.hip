@@ -1,12 +1,11 @@
 // Kernels of the AR consumer (`LARP_AR`, /root/reference/models/larp_ar.py:233-438) that the tokenizer path did
-// not already have.  Its matrix products are vt_gemm_nt / vt_gemm_tn_grouped, its training attention vt_attention_causal_*.
-//   rmsnorm       RMSNorm (models/norm.py:6-17): y = x * rsqrt(mean(x^2) + eps) * w, fp32 statistics, bf16 output for the next GEMM
+// not already have.  Its matrix products are vt_gemm_nt / vt_gemm_tn_grouped, its training attention vt_attention_causal_*, its RMSNorm
+// (models/norm.py:6-17) vt_rmsnorm_* (vt_rmsnorm.hip).
 //   swiglu        FeedForward (larp_ar.py:122-136): silu(w1 x) * (w3 x) on the packed projection h = [w3 x | w1 x]
 //   decode_attn   one new token against the KV cache (larp_ar.py:138-190 with `mask = causal_mask[:, None, input_pos]`): a GEMV-sized
 //                 softmax(q K^T / 8) V per (batch, head), memory-bound, one wave per (b, h)
 // All HBM-bound single passes, 8- or 16-byte accesses, rounding points of autocast(bf16).
 #include "vt_common.h"
-#include "vt_rmsnorm.h"
 
 namespace {
 
@@ -324,39 +323,6 @@ int grid_for(int64_t units) {
     return (int)(b < 1 ? 1 : b > 4096 ? 4096 : b);
 }
 }  // namespace
-
-#define RMS_DISPATCH(KERNEL, ...)                                                              \
-    switch (dim / 128) {                                                                       \
-        case 3: hipLaunchKernelGGL(KERNEL<3>, __VA_ARGS__); break;                             \
-        case 6: hipLaunchKernelGGL(KERNEL<6>, __VA_ARGS__); break;                             \
-        case 8: hipLaunchKernelGGL(KERNEL<8>, __VA_ARGS__); break;                             \
-        case 10: hipLaunchKernelGGL(KERNEL<10>, __VA_ARGS__); break;                           \
-        case 12: hipLaunchKernelGGL(KERNEL<12>, __VA_ARGS__); break;                           \
-        default: hipLaunchKernelGGL(KERNEL<20>, __VA_ARGS__); break;                           \
-    }
-
-static bool rms_dim_ok(int dim) { return dim == 384 || dim == 768 || dim == 1024 || dim == 1280 || dim == 1536 || dim == 2560; }
-
-extern "C" int vt_rmsnorm_fwd(const float* x, const float* w, float eps, int64_t rows, int32_t dim, void* y_bf16, float* rstd, vtStream stream) {
-    VT_CHECK_ARG(x && w && y_bf16 && rows > 0, "vt_rmsnorm_fwd: null pointer");
-    VT_CHECK_ARG(rms_dim_ok(dim), "vt_rmsnorm_fwd: width %d unsupported (384, 768, 1024, 1280, 1536, 2560: the llama-abs sizes)", dim);
-    const int grid = (int)((rows + 3) / 4 < 2048 ? (rows + 3) / 4 : 2048);
-    RMS_DISPATCH(rmsnorm_fwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, w, eps, rows, (bf16_t*)y_bf16, rstd)
-    VT_CHECK_LAUNCH("vt_rmsnorm_fwd");
-    return VT_OK;
-}
-
-extern "C" size_t vt_rmsnorm_bwd_workspace_bytes(int32_t dim) { return (size_t)RMS_BLOCKS * dim * sizeof(float); }
-
-extern "C" int vt_rmsnorm_bwd(const void* dy_bf16, const float* x, const float* w, const float* rstd, const float* dres, int64_t rows, int32_t dim,
-                              float* dx, void* dx_bf16, float* dw, void* workspace, vtStream stream) {
-    VT_CHECK_ARG(dy_bf16 && x && w && rstd && (dx || dx_bf16) && dw && workspace && rows > 0, "vt_rmsnorm_bwd: null pointer");
-    VT_CHECK_ARG(rms_dim_ok(dim), "vt_rmsnorm_bwd: width %d unsupported", dim);
-    float* part = (float*)workspace;
-    RMS_DISPATCH(rmsnorm_bwd_kernel, dim3(RMS_BLOCKS), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy_bf16, x, w, rstd, dres, rows, dx, (bf16_t*)dx_bf16, part)
-    VT_CHECK_LAUNCH("vt_rmsnorm_bwd");
-    return vt_sum_slabs(part, RMS_BLOCKS, (int64_t)dim, dim, dw, stream);
-}
 
 extern "C" int vt_swiglu_fwd(const void* h, int64_t M, int32_t I, void* a, vtStream stream) {
     VT_CHECK_ARG(h && a && M > 0 && I > 0 && I % 8 == 0, "vt_swiglu_fwd: null pointer or I %% 8 != 0");

@@ -13,6 +13,7 @@ typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
 typedef __attribute__((ext_vector_type(4))) short s16x4;
+typedef __attribute__((ext_vector_type(2))) float f32x2;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 
@@ -46,6 +47,8 @@ void vt_set_error(const char* fmt, ...);
 #define WS(T, off) ((T*)((char*)ws + (off)))   // typed pointer into the workspace `ws` of the enclosing function
 // (vt_vq.hip still has an int overload of its own for its kernel-launch arithmetic: call either with both arguments of one type)
 static inline size_t round_up(size_t a, size_t b) { return (a + b - 1) / b * b; }
+// what every kernel with 16-byte accesses asks of its buffers
+static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // ---- device helpers ----
 #if defined(__HIP_DEVICE_COMPILE__) || defined(__HIPCC__)
@@ -245,6 +248,10 @@ struct vtReduceItem {
 };
 #define VT_REDUCE_MAX_GROUP 16
 int vt_reduce_grouped(const vtReduceItem* items, int n, vtStream stream);
+// Per-block partial sums of a weight gradient -> the gradient: element t < nout is the sum over b < nblk of part[b * row_stride + t] and goes to
+// dst[t / 64][t % 64] (up to four destinations of 64 elements, fewer elements if nout says so; a null destination is skipped).  One wave per
+// element: lane l adds partials l, l + 64, ... in order, then wave_sum.  `who` names the launch in a failure's message.
+int vt_reduce_waves(const char* who, const float* part, int nblk, int64_t row_stride, int nout, float* d0, float* d1, float* d2, float* d3, vtStream stream);
 // LayerNorm backward without its reduction: partial sums go to `part` ([grid][3 * dim]); *nslab = grid
 int vt_layernorm_bwd_partials(const void* dy_bf16, const float* x, vtRowMap xmap, const float* gamma, const float* mean, const float* rstd,
                               const float* dres, int64_t rows, int32_t dim, float* dx, void* dx_bf16, float* part, int* nslab, vtStream stream);

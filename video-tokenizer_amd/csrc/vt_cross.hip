@@ -1,47 +1,15 @@
-// Row passes of model_design's CrossAttention layer (models/model_design/base/transformer.py:92-141) for gfx950.  Its GEMMs are
-// vt_gemm_nt / vt_gemm_tn_grouped, its attention vt_attention_cross_*, its gate vt_sigmoid_gate_cols_* (vt_gated.hip); here are
+// The row pass of model_design's CrossAttention layer (models/model_design/base/transformer.py:92-141) for gfx950.  Its GEMMs are
+// vt_gemm_nt / vt_gemm_tn_grouped, its attention vt_attention_cross_*, its gate vt_sigmoid_gate_cols_* (vt_gated.hip), its whole-row norms
+// norm_q / norm_kv (:108-109, :123-124) vt_rmsnorm_any_* (vt_rmsnorm.hip); here is
 //   head_rmsnorm  q_norm / k_norm (:18-27, :114-115, :134-135): RMSNorm over each 64-element head vector of a bf16 row
-//   rmsnorm_any   norm_q / norm_kv (:108-109, :123-124): vt_rmsnorm_* (vt_ar.hip) with the design widths 128 / 256 / 512 added
 // HBM-bound single passes with 16-byte accesses.  Rounding as the reference under autocast(bf16): the head norm reads the bf16 Linear
-// output and computes y = bf16(bf16(x * rstd) * w), rstd = rsqrt(mean(x^2) + eps) in fp32, w fp32.
+// output and computes y = bf16(bf16(x * rstd) * w), rstd = rsqrt(mean(x^2) + eps) in fp32, w fp32.  The statistics and the backward step are
+// vt_headvec.h's, shared with the fused q/k pass of vt_design.hip.
 #include "vt_common.h"
-#include "vt_rmsnorm.h"
+#include "vt_headvec.h"
 
 namespace {
-constexpr int HD = 64;       // head_dim (dim = 64 * heads at every size of the design)
-constexpr int VPB = 32;      // head vectors per 256-thread block: 8 lanes x 8 elements = one head vector, as vt_qknorm_rope_*
 constexpr int NBLK = 512;    // blocks of the backward = partial sums of dw: [NBLK, 64] fp32
-
-__device__ __forceinline__ float sum8(float v) {
-    v += __shfl_xor(v, 1);
-    v += __shfl_xor(v, 2);
-    v += __shfl_xor(v, 4);
-    return v;
-}
-
-struct Vec8 {
-    float v[8];
-};
-__device__ __forceinline__ Vec8 load8(const bf16_t* p) {
-    const bf16x8 r = *(const bf16x8*)p;
-    Vec8 o;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) o.v[i] = bf2f(r[i]);
-    return o;
-}
-__device__ __forceinline__ void store8(bf16_t* p, const Vec8& a) {
-    bf16x8 r;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) r[i] = f2bf(a.v[i]);
-    *(bf16x8*)p = r;
-}
-
-__device__ __forceinline__ float head_rstd(const Vec8& x, float eps) {
-    float ss = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) ss = fmaf(x.v[i], x.v[i], ss);
-    return __builtin_amdgcn_rsqf(sum8(ss) * (1.0f / HD) + eps);
-}
 
 __global__ __launch_bounds__(256) void head_rmsnorm_fwd_kernel(const bf16_t* __restrict__ x, int64_t x_rs, const float* __restrict__ w, float eps, int64_t M,
                                                                 int H, bf16_t* __restrict__ y, int64_t y_rs) {
@@ -62,8 +30,9 @@ __global__ __launch_bounds__(256) void head_rmsnorm_fwd_kernel(const bf16_t* __r
     }
 }
 
-// dx = rstd * g - x * rstd^3 / 64 * sum(x * g), g = w * dy (fp32, one rounding at the store); dw += dy * x * rstd (fp32: the forward's
-// rounding of x * rstd is not replayed, a step function inside a sum that is held to 1e-5).  dx may be dy's buffer: a lane reads its 16 bytes of dy before it writes the same 16 bytes of dx (no __restrict__ on the two).
+// head_rmsnorm_bwd_step per head vector (fp32, one rounding at the store of dx; in dw the forward's rounding of x * rstd is not replayed, a step
+// function inside a sum that is held to 1e-5).  dx may be dy's buffer: a lane reads its 16 bytes of dy before it writes the same 16 bytes of dx
+// (no __restrict__ on the two).
 // part: [NBLK, 64]
 __global__ __launch_bounds__(256) void head_rmsnorm_bwd_kernel(const bf16_t* dy, int64_t dy_rs, const bf16_t* __restrict__ x, int64_t x_rs,
                                                                 const float* __restrict__ w, float eps, int64_t M, int H, bf16_t* dx, int64_t dx_rs,
@@ -79,19 +48,7 @@ __global__ __launch_bounds__(256) void head_rmsnorm_bwd_kernel(const bf16_t* dy,
         const int col = (int)(vec % H) * HD + lane * 8;
         const Vec8 xv = load8(x + row * x_rs + col);
         const Vec8 gy = load8(dy + row * dy_rs + col);
-        const float rstd = head_rstd(xv, eps);
-        float g[8], dot = 0.f;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            g[i] = gy.v[i] * wr[i];
-            dot = fmaf(xv.v[i], g[i], dot);
-            aw[i] += gy.v[i] * (xv.v[i] * rstd);
-        }
-        const float k = sum8(dot) * rstd * rstd * rstd * (1.0f / HD);
-        Vec8 r;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) r.v[i] = g[i] * rstd - xv.v[i] * k;
-        store8(dx + row * dx_rs + col, r);
+        store8(dx + row * dx_rs + col, head_rmsnorm_bwd_step(xv, gy, wr, head_rstd(xv, eps), aw));
     }
 #pragma unroll
     for (int i = 0; i < 8; ++i) red[vslot][lane * 8 + i] = aw[i];
@@ -104,34 +61,8 @@ __global__ __launch_bounds__(256) void head_rmsnorm_bwd_kernel(const bf16_t* dy,
     }
 }
 
-// one wave per element of dw: lane l adds partials l, l + 64, ... in order, then a fixed butterfly
-__global__ __launch_bounds__(256) void head_rmsnorm_reduce_kernel(const float* __restrict__ part, int nblk, float* __restrict__ dw) {
-    const int e = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;   // e in [0, 64)
-    float s = 0.f;
-    for (int b = lane; b < nblk; b += 64) s += part[(int64_t)b * HD + e];
-    s = wave_sum(s);
-    if (lane == 0) dw[e] = s;
-}
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 bool head_stride_ok(int64_t rs, int H) { return rs >= (int64_t)HD * H && rs % 8 == 0; }
-bool rms_any_dim_ok(int dim) {
-    return dim == 128 || dim == 256 || dim == 512 || dim == 384 || dim == 768 || dim == 1024 || dim == 1280 || dim == 1536 || dim == 2560;
-}
 }  // namespace
-
-#define RMS_ANY_DISPATCH(KERNEL, ...)                                \
-    switch (dim / 128) {                                             \
-        case 1: hipLaunchKernelGGL(KERNEL<1>, __VA_ARGS__); break;   \
-        case 2: hipLaunchKernelGGL(KERNEL<2>, __VA_ARGS__); break;   \
-        case 3: hipLaunchKernelGGL(KERNEL<3>, __VA_ARGS__); break;   \
-        case 4: hipLaunchKernelGGL(KERNEL<4>, __VA_ARGS__); break;   \
-        case 6: hipLaunchKernelGGL(KERNEL<6>, __VA_ARGS__); break;   \
-        case 8: hipLaunchKernelGGL(KERNEL<8>, __VA_ARGS__); break;   \
-        case 10: hipLaunchKernelGGL(KERNEL<10>, __VA_ARGS__); break; \
-        case 12: hipLaunchKernelGGL(KERNEL<12>, __VA_ARGS__); break; \
-        default: hipLaunchKernelGGL(KERNEL<20>, __VA_ARGS__); break; \
-    }
 
 extern "C" int vt_head_rmsnorm_fwd(const void* x, int64_t x_rs, const float* w, float eps, int64_t M, int32_t H, void* y, int64_t y_rs, vtStream stream) {
     VT_CHECK_ARG(x && w && y, "vt_head_rmsnorm_fwd: null pointer");
@@ -168,29 +99,5 @@ extern "C" int vt_head_rmsnorm_bwd(const void* dy, int64_t dy_rs, const void* x,
     hipLaunchKernelGGL(head_rmsnorm_bwd_kernel, dim3(NBLK), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy, dy_rs, (const bf16_t*)x, x_rs, w, eps, M, H,
                        (bf16_t*)dx, dx_rs, (float*)workspace);
     VT_CHECK_LAUNCH("vt_head_rmsnorm_bwd");
-    hipLaunchKernelGGL(head_rmsnorm_reduce_kernel, dim3(HD / 4), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, NBLK, dw);
-    VT_CHECK_LAUNCH("vt_head_rmsnorm_bwd(reduce)");
-    return VT_OK;
-}
-
-extern "C" int vt_rmsnorm_any_fwd(const float* x, const float* w, float eps, int64_t rows, int32_t dim, void* y_bf16, float* rstd, vtStream stream) {
-    VT_CHECK_ARG(x && w && y_bf16 && rows > 0, "vt_rmsnorm_any_fwd: null pointer");
-    VT_CHECK_ARG(rms_any_dim_ok(dim), "vt_rmsnorm_any_fwd: width %d unsupported (128, 256, 512 and the widths of vt_rmsnorm_fwd)", dim);
-    const int grid = (int)((rows + 3) / 4 < 2048 ? (rows + 3) / 4 : 2048);
-    RMS_ANY_DISPATCH(rmsnorm_fwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, w, eps, rows, (bf16_t*)y_bf16, rstd)
-    VT_CHECK_LAUNCH("vt_rmsnorm_any_fwd");
-    return VT_OK;
-}
-
-extern "C" size_t vt_rmsnorm_any_bwd_workspace_bytes(int32_t dim) { return (size_t)RMS_BLOCKS * dim * sizeof(float); }
-
-extern "C" int vt_rmsnorm_any_bwd(const void* dy_bf16, const float* x, const float* w, const float* rstd, const float* dres, int64_t rows, int32_t dim,
-                                  float* dx, void* dx_bf16, float* dw, void* workspace, vtStream stream) {
-    VT_CHECK_ARG(dy_bf16 && x && w && rstd && (dx || dx_bf16) && dw && workspace && rows > 0, "vt_rmsnorm_any_bwd: null pointer");
-    VT_CHECK_ARG(rms_any_dim_ok(dim), "vt_rmsnorm_any_bwd: width %d unsupported", dim);
-    float* part = (float*)workspace;
-    RMS_ANY_DISPATCH(rmsnorm_bwd_kernel, dim3(RMS_BLOCKS), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy_bf16, x, w, rstd, dres, rows, dx, (bf16_t*)dx_bf16,
-                     part)
-    VT_CHECK_LAUNCH("vt_rmsnorm_any_bwd");
-    return vt_sum_slabs(part, RMS_BLOCKS, (int64_t)dim, dim, dw, stream);
+    return vt_reduce_waves("vt_head_rmsnorm_bwd(reduce)", (const float*)workspace, NBLK, HD, HD, dw, nullptr, nullptr, nullptr, stream);
 }

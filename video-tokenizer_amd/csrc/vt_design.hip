@@ -1,53 +1,19 @@
 // Row passes of model_design's self-attention block and stack (models/model_design/base/transformer.py:46-85, 148-216) for gfx950.
-// The GEMMs, the attention, the gate, GEGLU and the bf16-output RMSNorm are the kernels the other layers already use; new here:
+// The GEMMs, the attention, the gate, GEGLU and the whole-row RMSNorms (vt_rmsnorm_any_*, vt_rmsnorm_any_f32_* for final_norm: vt_rmsnorm.hip)
+// are the kernels the other layers already use; new here:
 //   qkrms_rope      q_norm / k_norm (RMSNorm per 64-wide head, weight only, :76-77) and the rotary embedding (:79-80) of q and k, v copied:
 //                   reads columns q | k | v of the [M, 4D] output of ONE GEMM on [to_qkv ; to_gate], writes the packed [M, 3D] operand of
-//                   vt_attention_fwd.  The RMS twin of vt_qknorm_rope_* (vt_gated.hip); bit for bit vt_head_rmsnorm_* + vt_rope_rotate.
+//                   vt_attention_fwd.  The RMS twin of vt_qknorm_rope_* (vt_gated.hip); bit for bit vt_head_rmsnorm_* + vt_rope_rotate: the
+//                   norm's statistics and backward step are the same functions of vt_headvec.h that vt_cross.hip calls.
 //   residual_scale  x + res_scale * f(x) (:176-183) with res_scale a 0-dim PARAMETER read from device memory (no host read, capturable),
 //                   and its backward with the full-reduction gradient of the scale from fixed-order partial sums.
-//   rmsnorm_any_f32 final_norm (:211, :216): RMSNorm of the fp32 residual stream with an fp32, unrounded output and an fp32 incoming gradient.
 // HBM-bound single passes, 16 bytes per lane and access, no float atomics, no device trigonometry (cos / sin come from the tables).
 #include "vt_common.h"
-#include "vt_rmsnorm.h"
+#include "vt_headvec.h"
 
 namespace {
-constexpr int HD = 64;        // head_dim (dim = 64 * heads at every size of the design)
-constexpr int VPB = 32;       // head vectors per 256-thread block: 8 lanes x 8 elements = one head vector
 constexpr int NBLK = 512;     // blocks per operand of the q/k backward = partial sums of dq_w / dk_w: [NBLK, 2, 64] fp32
 constexpr int RS_BLOCKS = 256;   // blocks of the scaled-residual backward = partial sums of d(res_scale)
-
-__device__ __forceinline__ float sum8(float v) {
-    v += __shfl_xor(v, 1);
-    v += __shfl_xor(v, 2);
-    v += __shfl_xor(v, 4);
-    return v;
-}
-
-struct Vec8 {
-    float v[8];
-};
-__device__ __forceinline__ Vec8 load8(const bf16_t* p) {
-    const bf16x8 r = *(const bf16x8*)p;
-    Vec8 o;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) o.v[i] = bf2f(r[i]);
-    return o;
-}
-__device__ __forceinline__ void store8(bf16_t* p, const Vec8& a) {
-    bf16x8 r;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) r[i] = f2bf(a.v[i]);
-    *(bf16x8*)p = r;
-}
-
-// the statistics of vt_head_rmsnorm_* (vt_cross.hip).  Here and below the multiply-adds that the compiler contracts in those kernels are written
-// out as fmaf, so that the bit-for-bit agreement with the chain of passes does not hang on its choice of which product to fuse
-__device__ __forceinline__ float head_rstd(const Vec8& x, float eps) {
-    float ss = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) ss = fmaf(x.v[i], x.v[i], ss);
-    return __builtin_amdgcn_rsqf(fmaf(sum8(ss), 1.0f / HD, eps));
-}
 
 // the rotation of vt_rope_rotate (vt_rope.hip): x holds bf16 values, sgn = 1 (forward) or -1 (conjugate).  That kernel rounds b sin in the
 // first and a sin in the second component and fuses the cos products (read off its ISA); the same here
@@ -93,8 +59,8 @@ __global__ __launch_bounds__(256) void qkrms_rope_fwd_kernel(const bf16_t* __res
     }
 }
 
-// grid (NBLK, 3).  part: [NBLK, 2(which), 64].  dq / dk: conjugate rotation rounded to bf16 (autograd rounds there), then the backward of
-// vt_head_rmsnorm_bwd with rstd recomputed from qkvg: dx = rstd g - x rstd^3 / 64 sum(x g), g = w dy; dw += dy x rstd in fp32.
+// grid (NBLK, 3).  part: [NBLK, 2(which), 64].  dq / dk: conjugate rotation rounded to bf16 (autograd rounds there), then the backward step of
+// vt_head_rmsnorm_bwd with rstd recomputed from qkvg.
 __global__ __launch_bounds__(256) void qkrms_rope_bwd_kernel(const bf16_t* __restrict__ qkvg, int64_t in_rs, const bf16_t* __restrict__ dqkv, int64_t M, int L,
                                                               int H, const float* __restrict__ q_w, const float* __restrict__ k_w, float eps,
                                                               const float* __restrict__ cs, const float* __restrict__ sn, bf16_t* __restrict__ dqkvg,
@@ -119,19 +85,7 @@ __global__ __launch_bounds__(256) void qkrms_rope_bwd_kernel(const bf16_t* __res
         Vec8 gy = rotate8(load8(gsrc), cs + pos * (HD / 2), sn + pos * (HD / 2), lane, sgn);
 #pragma unroll
         for (int i = 0; i < 8; ++i) gy.v[i] = round_bf16(gy.v[i]);
-        const float rstd = head_rstd(xv, eps);
-        float g[8], dot = 0.f;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            g[i] = gy.v[i] * wr[i];
-            dot = fmaf(xv.v[i], g[i], dot);
-            aw[i] = fmaf(gy.v[i], xv.v[i] * rstd, aw[i]);
-        }
-        const float k = sum8(dot) * rstd * rstd * rstd * (1.0f / HD);
-        Vec8 r;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) r.v[i] = fmaf(g[i], rstd, -(xv.v[i] * k));
-        store8(dst, r);
+        store8(dst, head_rmsnorm_bwd_step(xv, gy, wr, head_rstd(xv, eps), aw));
     }
     if (which == 2) return;
 #pragma unroll
@@ -143,16 +97,6 @@ __global__ __launch_bounds__(256) void qkrms_rope_bwd_kernel(const bf16_t* __res
         for (int v = 0; v < VPB; ++v) t += red[v][threadIdx.x];
         part[((int64_t)blockIdx.x * 2 + which) * HD + threadIdx.x] = t;
     }
-}
-
-// one wave per output element (which, e): lane l adds partials l, l + 64, ... in order, then a fixed butterfly
-__global__ __launch_bounds__(256) void qkrms_reduce_kernel(const float* __restrict__ part, int nblk, float* dq_w, float* dk_w) {
-    const int t = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;   // t in [0, 128)
-    float s = 0.f;
-    for (int b = lane; b < nblk; b += 64) s += part[(int64_t)b * 2 * HD + t];
-    s = wave_sum(s);
-    float* dst = t < HD ? dq_w : dk_w;
-    if (dst && lane == 0) dst[t & 63] = s;
 }
 
 // ---- scaled residual.  torch multiplies the bf16 tensor y by the 0-dim fp32 parameter in bf16: the parameter is converted to the common
@@ -196,94 +140,8 @@ __global__ __launch_bounds__(256) void residual_scale_bwd_kernel(const float* __
     if (threadIdx.x == 0) part[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
 }
 
-__global__ __launch_bounds__(64) void residual_scale_reduce_kernel(const float* __restrict__ part, int nblk, float* __restrict__ ds) {
-    float s = 0.f;
-    for (int b = threadIdx.x; b < nblk; b += 64) s += part[b];
-    s = wave_sum(s);
-    if (threadIdx.x == 0) *ds = s;
-}
-
-// ---- RMSNorm with fp32 output and fp32 incoming gradient: the layout of vt_rmsnorm.h (one wave per row, lane l owns the float2 pieces
-// j * 64 + l), without the bf16 rounding of the output and of dy
-template <int J>
-__global__ __launch_bounds__(256) void rmsnorm_f32_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w, float eps, int64_t rows,
-                                                               float* __restrict__ y, float* __restrict__ rstd_out) {
-    constexpr int dim = J * 128;
-    const int lane = threadIdx.x & 63;
-    for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < rows; r += (int64_t)gridDim.x * 4) {
-        const f32x2* xr = (const f32x2*)(x + r * dim);
-        f32x2 v[J];
-        float ss = 0.f;
-#pragma unroll
-        for (int j = 0; j < J; ++j) {
-            v[j] = xr[j * 64 + lane];
-            ss = fmaf(v[j][0], v[j][0], ss);
-            ss = fmaf(v[j][1], v[j][1], ss);
-        }
-        ss = wave_sum(ss);
-        const float rstd = __builtin_amdgcn_rsqf(ss * (1.0f / dim) + eps);
-        if (lane == 0 && rstd_out) rstd_out[r] = rstd;
-        f32x2* yr = (f32x2*)(y + r * dim);
-#pragma unroll
-        for (int j = 0; j < J; ++j) yr[j * 64 + lane] = v[j] * rstd * ((const f32x2*)w)[j * 64 + lane];
-    }
-}
-
-template <int J>
-__global__ __launch_bounds__(256) void rmsnorm_f32_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ w,
-                                                               const float* __restrict__ rstd_in, int64_t rows, float* __restrict__ dx,
-                                                               float* __restrict__ dw_part) {
-    constexpr int dim = J * 128;
-    __shared__ float red[4][dim];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    f32x2 dwacc[J];
-#pragma unroll
-    for (int j = 0; j < J; ++j) dwacc[j] = (f32x2){0.f, 0.f};
-    for (int64_t r = (int64_t)blockIdx.x * 4 + wv; r < rows; r += (int64_t)gridDim.x * 4) {
-        const f32x2* xr = (const f32x2*)(x + r * dim);
-        const f32x2* dyr = (const f32x2*)(dy + r * dim);
-        const float rstd = rstd_in[r];
-        f32x2 xv[J], g[J];
-        float dot = 0.f;
-#pragma unroll
-        for (int j = 0; j < J; ++j) {
-            xv[j] = xr[j * 64 + lane];
-            const f32x2 dyf = dyr[j * 64 + lane];
-            g[j] = dyf * ((const f32x2*)w)[j * 64 + lane];
-            dot = fmaf(xv[j][0], g[j][0], dot);
-            dot = fmaf(xv[j][1], g[j][1], dot);
-            dwacc[j] += dyf * xv[j] * rstd;
-        }
-        dot = wave_sum(dot);
-        const float k = dot * rstd * rstd * rstd * (1.0f / dim);
-#pragma unroll
-        for (int j = 0; j < J; ++j) ((f32x2*)(dx + r * dim))[j * 64 + lane] = g[j] * rstd - xv[j] * k;
-    }
-#pragma unroll
-    for (int j = 0; j < J; ++j) ((f32x2*)red[wv])[j * 64 + lane] = dwacc[j];
-    __syncthreads();
-    for (int c = threadIdx.x; c < dim; c += 256) dw_part[(int64_t)blockIdx.x * dim + c] = red[0][c] + red[1][c] + red[2][c] + red[3][c];
-}
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 bool stride_ok(int64_t rs, int H) { return rs >= (int64_t)3 * HD * H && rs % 8 == 0; }
-bool rms_dim_ok(int dim) {
-    return dim == 128 || dim == 256 || dim == 512 || dim == 384 || dim == 768 || dim == 1024 || dim == 1280 || dim == 1536 || dim == 2560;
-}
 }  // namespace
-
-#define RMS_F32_DISPATCH(KERNEL, ...)                                \
-    switch (dim / 128) {                                             \
-        case 1: hipLaunchKernelGGL(KERNEL<1>, __VA_ARGS__); break;   \
-        case 2: hipLaunchKernelGGL(KERNEL<2>, __VA_ARGS__); break;   \
-        case 3: hipLaunchKernelGGL(KERNEL<3>, __VA_ARGS__); break;   \
-        case 4: hipLaunchKernelGGL(KERNEL<4>, __VA_ARGS__); break;   \
-        case 6: hipLaunchKernelGGL(KERNEL<6>, __VA_ARGS__); break;   \
-        case 8: hipLaunchKernelGGL(KERNEL<8>, __VA_ARGS__); break;   \
-        case 10: hipLaunchKernelGGL(KERNEL<10>, __VA_ARGS__); break; \
-        case 12: hipLaunchKernelGGL(KERNEL<12>, __VA_ARGS__); break; \
-        default: hipLaunchKernelGGL(KERNEL<20>, __VA_ARGS__); break; \
-    }
 
 extern "C" int vt_qkrms_rope_fwd(const void* qkvg, int64_t in_rs, int64_t M, int32_t L, int32_t H, const float* q_w, const float* k_w, float eps,
                                  const float* cos_tab, const float* sin_tab, void* qkv_out, int64_t out_rs, vtStream stream) {
@@ -315,11 +173,8 @@ extern "C" int vt_qkrms_rope_bwd(const void* qkvg, int64_t in_rs, const void* dq
     hipLaunchKernelGGL(qkrms_rope_bwd_kernel, dim3(NBLK, 3), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)qkvg, in_rs, (const bf16_t*)dqkv, M, L, H, q_w,
                        k_w, eps, cos_tab, sin_tab, (bf16_t*)dqkvg, out_rs, -1.0f, (float*)workspace);
     VT_CHECK_LAUNCH("vt_qkrms_rope_bwd");
-    if (dq_w || dk_w) {
-        hipLaunchKernelGGL(qkrms_reduce_kernel, dim3(2 * HD / 4), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, NBLK, dq_w, dk_w);
-        VT_CHECK_LAUNCH("vt_qkrms_rope_bwd(reduce)");
-    }
-    return VT_OK;
+    if (!dq_w && !dk_w) return VT_OK;
+    return vt_reduce_waves("vt_qkrms_rope_bwd(reduce)", (const float*)workspace, NBLK, 2 * HD, 2 * HD, dq_w, dk_w, nullptr, nullptr, stream);
 }
 
 static int rs_grid(int64_t n4, int cap) {
@@ -350,32 +205,6 @@ extern "C" int vt_residual_scale_bwd(const float* dout, const float* y, const fl
     const int grid = rs_grid(n4, RS_BLOCKS);
     hipLaunchKernelGGL(residual_scale_bwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, dout, y, scale_dev, n4, dy, dscale ? (float*)workspace : nullptr);
     VT_CHECK_LAUNCH("vt_residual_scale_bwd");
-    if (dscale) {
-        hipLaunchKernelGGL(residual_scale_reduce_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const float*)workspace, grid, dscale);
-        VT_CHECK_LAUNCH("vt_residual_scale_bwd(reduce)");
-    }
-    return VT_OK;
-}
-
-extern "C" int vt_rmsnorm_any_f32_fwd(const float* x, const float* w, float eps, int64_t rows, int32_t dim, float* y, float* rstd, vtStream stream) {
-    VT_CHECK_ARG(x && w && y && rows > 0, "vt_rmsnorm_any_f32_fwd: null pointer");
-    VT_CHECK_ARG(rms_dim_ok(dim), "vt_rmsnorm_any_f32_fwd: width %d unsupported (the widths of vt_rmsnorm_any_fwd)", dim);
-    VT_CHECK_ARG(aligned16(x) && aligned16(w) && aligned16(y), "vt_rmsnorm_any_f32_fwd: buffers must be 16-byte aligned");
-    const int grid = (int)((rows + 3) / 4 < 2048 ? (rows + 3) / 4 : 2048);
-    RMS_F32_DISPATCH(rmsnorm_f32_fwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, w, eps, rows, y, rstd)
-    VT_CHECK_LAUNCH("vt_rmsnorm_any_f32_fwd");
-    return VT_OK;
-}
-
-extern "C" size_t vt_rmsnorm_any_f32_bwd_workspace_bytes(int32_t dim) { return (size_t)RMS_BLOCKS * dim * sizeof(float); }
-
-extern "C" int vt_rmsnorm_any_f32_bwd(const float* dy, const float* x, const float* w, const float* rstd, int64_t rows, int32_t dim, float* dx, float* dw,
-                                      void* workspace, vtStream stream) {
-    VT_CHECK_ARG(dy && x && w && rstd && dx && dw && workspace && rows > 0, "vt_rmsnorm_any_f32_bwd: null pointer");
-    VT_CHECK_ARG(rms_dim_ok(dim), "vt_rmsnorm_any_f32_bwd: width %d unsupported (the widths of vt_rmsnorm_any_fwd)", dim);
-    VT_CHECK_ARG(aligned16(dy) && aligned16(x) && aligned16(w) && aligned16(dx) && aligned16(workspace), "vt_rmsnorm_any_f32_bwd: buffers must be 16-byte aligned");
-    float* part = (float*)workspace;
-    RMS_F32_DISPATCH(rmsnorm_f32_bwd_kernel, dim3(RMS_BLOCKS), dim3(256), 0, (hipStream_t)stream, dy, x, w, rstd, rows, dx, part)
-    VT_CHECK_LAUNCH("vt_rmsnorm_any_f32_bwd");
-    return vt_sum_slabs(part, RMS_BLOCKS, (int64_t)dim, dim, dw, stream);
+    if (!dscale) return VT_OK;
+    return vt_reduce_waves("vt_residual_scale_bwd(reduce)", (const float*)workspace, grid, 1, 1, dscale, nullptr, nullptr, nullptr, stream);
 }

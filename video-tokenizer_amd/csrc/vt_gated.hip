@@ -13,35 +13,10 @@
 // cat/chunk copies are needed.  Rounding points follow autocast(bf16): LayerNorm output, rotary output, sigmoid, gelu and
 // every product are rounded to bf16 where the reference materialises a bf16 tensor; statistics and products are fp32.
 #include "vt_common.h"
+#include "vt_headvec.h"
 
 namespace {
-constexpr int HD = 64;       // head_dim of every model size (models/model_new/base/utils.py:6)
-constexpr int VPB = 32;      // head vectors per 256-thread block (8 lanes x 8 elements = one head vector)
 constexpr int NBLK = 512;    // blocks per operand in the backward (partial sums: [NBLK, 2, 2, 64] fp32)
-
-__device__ __forceinline__ float sum8(float v) {
-    v += __shfl_xor(v, 1);
-    v += __shfl_xor(v, 2);
-    v += __shfl_xor(v, 4);
-    return v;
-}
-
-struct Vec8 {
-    float v[8];
-};
-__device__ __forceinline__ Vec8 load8(const bf16_t* p) {
-    const bf16x8 r = *(const bf16x8*)p;
-    Vec8 o;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) o.v[i] = bf2f(r[i]);
-    return o;
-}
-__device__ __forceinline__ void store8(bf16_t* p, const Vec8& a) {
-    bf16x8 r;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) r[i] = f2bf(a.v[i]);
-    *(bf16x8*)p = r;
-}
 
 // LayerNorm statistics of one 64-vector spread over 8 lanes (biased variance, two passes in registers)
 __device__ __forceinline__ void ln_stats(const Vec8& x, float eps, float& mean, float& rstd) {
@@ -158,16 +133,6 @@ __global__ __launch_bounds__(256) void qknorm_rope_bwd_kernel(const bf16_t* __re
     }
 }
 
-// one wave per output element (which, w|b, e): lane l adds partials l, l + 64, ... in order, then a fixed butterfly
-__global__ __launch_bounds__(256) void qknorm_reduce_kernel(const float* __restrict__ part, int nblk, float* dq_w, float* dq_b, float* dk_w, float* dk_b) {
-    const int t = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;   // t in [0, 256)
-    float s = 0.f;
-    for (int b = lane; b < nblk; b += 64) s += part[(int64_t)b * 256 + t];
-    s = wave_sum(s);
-    float* dst = (t >> 6) == 0 ? dq_w : (t >> 6) == 1 ? dq_b : (t >> 6) == 2 ? dk_w : dk_b;
-    if (dst && lane == 0) dst[t & 63] = s;
-}
-
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + __expf(-x)); }
 
 // gate: first gate column of row 0, gate_rs its row stride (the block's gate is qkvg + 3D with stride 4D; vt_sigmoid_gate_cols_* takes any)
@@ -240,7 +205,6 @@ int grid_for(int64_t units) {
     const int64_t b = (units + 255) / 256;
     return (int)(b < 1 ? 1 : b > 4096 ? 4096 : b);
 }
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 }  // namespace
 
 extern "C" int vt_qknorm_rope_fwd(const void* qkvg, int64_t M, int32_t L, int32_t H, const float* q_w, const float* q_b, const float* k_w,
@@ -268,9 +232,7 @@ extern "C" int vt_qknorm_rope_bwd(const void* qkvg, const void* dqkv, int64_t M,
     hipLaunchKernelGGL(qknorm_rope_bwd_kernel, dim3(NBLK, 3), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)qkvg, (const bf16_t*)dqkv, M, L, H, q_w, k_w,
                        eps, cos_tab, sin_tab, (bf16_t*)dqkvg, (float*)workspace);
     VT_CHECK_LAUNCH("vt_qknorm_rope_bwd");
-    hipLaunchKernelGGL(qknorm_reduce_kernel, dim3(64), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, NBLK, dq_w, dq_b, dk_w, dk_b);
-    VT_CHECK_LAUNCH("vt_qknorm_rope_bwd(reduce)");
-    return VT_OK;
+    return vt_reduce_waves("vt_qknorm_rope_bwd(reduce)", (const float*)workspace, NBLK, 4 * HD, 4 * HD, dq_w, dq_b, dk_w, dk_b, stream);
 }
 
 // `who`: the entry point's name, so that a refusal or a launch failure is reported under the caller's own name

@@ -179,6 +179,19 @@ static void launch_reduce_partials(const float* partial, int nslab, int64_t slab
     else hipLaunchKernelGGL(reduce_partials_kernel<8>, grid, dim3(256), 0, s, partial, nslab, slab_stride, width, ro);
 }
 
+// the reducer of the head-vector row passes (vt_reduce_waves, vt_common.h): one wave per output element t, lane l adds partials l, l + 64, ...
+// in order, then the fixed butterfly of wave_sum; element t belongs to destination t / 64
+__global__ __launch_bounds__(256) void reduce_waves_kernel(const float* __restrict__ part, int nblk, int64_t row_stride, int nout, float* d0, float* d1,
+                                                            float* d2, float* d3) {
+    const int t = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (t >= nout) return;      // uniform per wave
+    float s = 0.f;
+    for (int b = lane; b < nblk; b += 64) s += part[(int64_t)b * row_stride + t];
+    s = wave_sum(s);
+    float* dst = (t >> 6) == 0 ? d0 : (t >> 6) == 1 ? d1 : (t >> 6) == 2 ? d2 : d3;
+    if (dst && lane == 0) dst[t & 63] = s;
+}
+
 // several reductions in one launch (blockIdx.z = item); per item the arithmetic of reduce_partials_kernel<lanes>
 struct ReduceGroup {
     vtReduceItem it[VT_REDUCE_MAX_GROUP];
@@ -389,6 +402,12 @@ __global__ __launch_bounds__(256) void pack_weight_group_kernel(const PackGroup 
 }
 
 }  // namespace
+
+int vt_reduce_waves(const char* who, const float* part, int nblk, int64_t row_stride, int nout, float* d0, float* d1, float* d2, float* d3, vtStream stream) {
+    hipLaunchKernelGGL(reduce_waves_kernel, dim3((nout + 3) / 4), dim3(256), 0, (hipStream_t)stream, part, nblk, row_stride, nout, d0, d1, d2, d3);
+    VT_CHECK_LAUNCH(who);
+    return VT_OK;
+}
 
 int vt_reduce_grouped(const vtReduceItem* items, int n, vtStream stream) {
     VT_CHECK_ARG(items && n > 0 && n <= VT_REDUCE_MAX_GROUP, "vt_reduce_grouped: 1..%d items", VT_REDUCE_MAX_GROUP);

@@ -45,8 +45,6 @@ __global__ __launch_bounds__(kMaxThreads) void rope_rotate_kernel(bf16_t* __rest
     }
 }
 
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace
 
 extern "C" int vt_rope_rotate(void* qkv, int64_t ld, int64_t M, int32_t L, int32_t H, const float* cos_tab, const float* sin_tab,

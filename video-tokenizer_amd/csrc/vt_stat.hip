@@ -196,7 +196,6 @@ __global__ __launch_bounds__(256) void stat_partial_sum_kernel(const float* __re
     }
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 int check_common(const char* name, const void* z, int64_t M, int32_t W, int32_t d, const int32_t* levels_host, int64_t ld, FsqConsts& k) {
     VT_CHECK_ARG(M > 0 && W >= 128 && W <= 1024 && W % 128 == 0, "%s: need M > 0 and W a multiple of 128 in [128, 1024] (M = %lld, W = %d)", name,

@@ -21,7 +21,7 @@ from .fsq import FSQ
 from .registry import register
 from .titok import get_model_dims, rope_tables
 
-RMS_WIDTHS = (128, 256, 384, 512, 768, 1024, 1280, 1536, 2560)      # vt_rmsnorm_any_*
+RMS_WIDTHS = (128, 256, 384, 512, 768, 1024, 1280, 1536, 2560)      # vt_rmsnorm_any_* (RMS_WIDTHS of csrc/vt_rmsnorm.hip)
 
 
 class RMSNorm(nn.Module):
@@ -291,7 +291,7 @@ class UnifiedDecoder(nn.Module, _Tables):
     def _context(self, cond):
         ad = self.cond_adapter
         c = F_.Linear.apply(cond, self.proj_cond.weight, self.proj_cond.bias)                       # bf16 values
-        t = F_.Linear.apply(F_.RMSNormRows.apply(c, ad[0].weight, ad[0].eps), ad[1].weight, None)
+        t = F_.Linear.apply(F_.RMSNormRows.apply(c, ad[0].weight, ad[0].eps, "rmsnorm_any"), ad[1].weight, None)
         t = F_.Linear.apply(TF.silu(t.bfloat16()).float(), ad[3].weight, None)
         return (c.bfloat16() + t.bfloat16()).float()
 

@@ -557,23 +557,25 @@ class ResidualScale(torch.autograd.Function):
 
 
 class RMSNormRows(torch.autograd.Function):
-    """RMSNorm (transformer.py:18-27) of rows that a bf16 Linear reads next, on vt_rmsnorm_any_*: fp32 in, the bf16-rounded output returned in
-    an fp32 tensor (cond_adapter.0 of the design's decoder)."""
+    """RMSNorm (transformer.py:18-27; models/norm.py:6-17) of rows that a bf16 Linear reads next: fp32 in, the bf16-rounded output returned in an
+    fp32 tensor.  `family` names the pair of hip wrappers, i.e. the entry-point family of vt_rmsnorm.hip: "rmsnorm_any" (cond_adapter.0 of the
+    design's decoder) or "rmsnorm" (the llama-abs widths only: the norms of larp_ar)."""
 
     @staticmethod
-    def forward(ctx, x, weight, eps):
+    def forward(ctx, x, weight, eps, family):
         hip.require_gpu(x, weight)
         x2 = x.contiguous().reshape(-1, x.shape[-1]).float()
         w = weight.detach().float().contiguous()
-        y, rstd = hip.rmsnorm_any_fwd(x2, w, eps)
+        y, rstd = getattr(hip, family + "_fwd")(x2, w, eps)
         ctx.save_for_backward(x2, w, rstd)
+        ctx.family = family
         return y.float().reshape(x.shape)
 
     @staticmethod
     def backward(ctx, dy):
         x2, w, rstd = ctx.saved_tensors
-        dx, _, dw = hip.rmsnorm_any_bwd(hip.cast_rows(dy.contiguous().reshape(x2.shape).float()), x2, w, rstd)
-        return dx.reshape(dy.shape), dw if ctx.needs_input_grad[1] else None, None
+        dx, _, dw = getattr(hip, ctx.family + "_bwd")(hip.cast_rows(dy.contiguous().reshape(x2.shape).float()), x2, w, rstd)
+        return dx.reshape(dy.shape), dw if ctx.needs_input_grad[1] else None, None, None
 
 
 class RMSNormF32(torch.autograd.Function):

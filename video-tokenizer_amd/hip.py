@@ -41,7 +41,6 @@ class GemmTN(ctypes.Structure):
 GEMM_TILE = 0
 
 
-
 # every symbol include/vt_hip.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "vt_abi_version": (c_i32, []),
@@ -236,8 +235,6 @@ def lib():
             fn.argtypes = args
         _lib = L
     return _lib
-
-
 
 
 class HipError(RuntimeError):
@@ -568,48 +565,49 @@ def sigmoid_gate_cols_bwd(dog, o, gate, dgate):
     return d_o
 
 
+def _rmsnorm_fwd(family, x, w, eps, out_dtype=torch.bfloat16):
+    """the forward of one RMSNorm entry-point family (`vt_rmsnorm`, `vt_rmsnorm_any`, `vt_rmsnorm_any_f32`) -> (y out_dtype, rstd fp32 [rows])"""
+    rows, dim = x.shape
+    y = torch.empty(rows, dim, device=x.device, dtype=out_dtype)
+    rstd = torch.empty(rows, device=x.device, dtype=torch.float32)
+    check(getattr(lib(), family + "_fwd")(ptr(x), ptr(w), eps, rows, dim, ptr(y), ptr(rstd), stream()), family + "_fwd")
+    return y, rstd
+
+
+def _rmsnorm_bwd(family, dy, x, w, rstd, dres=None, want_bf16=False):
+    """the backward of one family -> (dx, dxb, dw).  The fp32 family's C signature has neither dres nor the bf16 copy dxb"""
+    rows, dim = x.shape
+    bf16 = not family.endswith("_f32")
+    dx = torch.empty_like(x)
+    dxb = torch.empty(rows, dim, device=x.device, dtype=torch.bfloat16) if want_bf16 else None
+    dw = torch.empty(dim, device=x.device, dtype=torch.float32)
+    ws = _ws(getattr(lib(), family + "_bwd_workspace_bytes")(dim), x.device)
+    args = (ptr(dy), ptr(x), ptr(w), ptr(rstd)) + ((ptr(dres),) if bf16 else ()) + (rows, dim, ptr(dx)) + ((ptr(dxb),) if bf16 else ())
+    check(getattr(lib(), family + "_bwd")(*args, ptr(dw), ptr(ws), stream()), family + "_bwd")
+    return dx, dxb, dw
+
+
 def rmsnorm_any_fwd(x, w, eps):
     """vt_rmsnorm_fwd at the widths of model_design as well (128, 256, 512)"""
     require_gpu(x, w)
-    rows, dim = x.shape
     assert x.dtype == torch.float32 and x.is_contiguous() and w.dtype == torch.float32 and w.is_contiguous()
-    y = torch.empty(rows, dim, device=x.device, dtype=torch.bfloat16)
-    rstd = torch.empty(rows, device=x.device, dtype=torch.float32)
-    check(lib().vt_rmsnorm_any_fwd(ptr(x), ptr(w), eps, rows, dim, ptr(y), ptr(rstd), stream()), "vt_rmsnorm_any_fwd")
-    return y, rstd
+    return _rmsnorm_fwd("vt_rmsnorm_any", x, w, eps)
 
 
 def rmsnorm_any_bwd(dy, x, w, rstd, dres=None, want_bf16=False):
     require_gpu(dy, x, w, rstd, dres)
-    rows, dim = x.shape
-    assert dy.is_contiguous() and dy.dtype == torch.bfloat16 and tuple(dy.shape) == (rows, dim)
-    dx = torch.empty_like(x)
-    dxb = torch.empty(rows, dim, device=x.device, dtype=torch.bfloat16) if want_bf16 else None
-    dw = torch.empty(dim, device=x.device, dtype=torch.float32)
-    ws = _ws(lib().vt_rmsnorm_any_bwd_workspace_bytes(dim), x.device)
-    check(lib().vt_rmsnorm_any_bwd(ptr(dy), ptr(x), ptr(w), ptr(rstd), ptr(dres), rows, dim, ptr(dx), ptr(dxb), ptr(dw), ptr(ws), stream()),
-          "vt_rmsnorm_any_bwd")
-    return dx, dxb, dw
+    assert dy.is_contiguous() and dy.dtype == torch.bfloat16 and tuple(dy.shape) == tuple(x.shape)
+    return _rmsnorm_bwd("vt_rmsnorm_any", dy, x, w, rstd, dres, want_bf16)
 
 
 def rmsnorm_fwd(x, w, eps):
     require_gpu(x, w)
-    rows, dim = x.shape
-    y = torch.empty(rows, dim, device=x.device, dtype=torch.bfloat16)
-    rstd = torch.empty(rows, device=x.device, dtype=torch.float32)
-    check(lib().vt_rmsnorm_fwd(ptr(x), ptr(w), eps, rows, dim, ptr(y), ptr(rstd), stream()), "vt_rmsnorm_fwd")
-    return y, rstd
+    return _rmsnorm_fwd("vt_rmsnorm", x, w, eps)
 
 
 def rmsnorm_bwd(dy, x, w, rstd, dres=None, want_bf16=False):
     require_gpu(dy, x, w, rstd)
-    rows, dim = x.shape
-    dx = torch.empty_like(x)
-    dxb = torch.empty(rows, dim, device=x.device, dtype=torch.bfloat16) if want_bf16 else None
-    dw = torch.empty(dim, device=x.device, dtype=torch.float32)
-    ws = _ws(lib().vt_rmsnorm_bwd_workspace_bytes(dim), x.device)
-    check(lib().vt_rmsnorm_bwd(ptr(dy), ptr(x), ptr(w), ptr(rstd), ptr(dres), rows, dim, ptr(dx), ptr(dxb), ptr(dw), ptr(ws), stream()), "vt_rmsnorm_bwd")
-    return dx, dxb, dw
+    return _rmsnorm_bwd("vt_rmsnorm", dy, x, w, rstd, dres, want_bf16)
 
 
 def swiglu_fwd(h):
@@ -899,7 +897,7 @@ def geglu_bwd(da, h):
     return dh
 
 
-# ---- row passes of model_design's self-attention block and stack (csrc/vt_design.hip) ----
+# ---- row passes of model_design's self-attention block and stack (csrc/vt_design.hip; its final norm csrc/vt_rmsnorm.hip) ----
 def _tables_ok(cos, sin, L):
     return cos.dtype == torch.float32 and sin.dtype == torch.float32 and cos.is_contiguous() and sin.is_contiguous() and cos.shape == (L, 32) == sin.shape
 
@@ -958,21 +956,13 @@ def residual_scale_bwd(dout, y, scale, want_ds=True):
 def rmsnorm_any_f32_fwd(x, w, eps):
     """RMSNorm with an fp32, unrounded output (final_norm of model_design's stack): -> (y fp32, rstd fp32 [rows])"""
     require_gpu(x, w)
-    rows, dim = x.shape
     assert x.dtype == torch.float32 and x.is_contiguous() and w.dtype == torch.float32 and w.is_contiguous()
-    y = torch.empty_like(x)
-    rstd = torch.empty(rows, device=x.device, dtype=torch.float32)
-    check(lib().vt_rmsnorm_any_f32_fwd(ptr(x), ptr(w), eps, rows, dim, ptr(y), ptr(rstd), stream()), "vt_rmsnorm_any_f32_fwd")
-    return y, rstd
+    return _rmsnorm_fwd("vt_rmsnorm_any_f32", x, w, eps, out_dtype=torch.float32)
 
 
 def rmsnorm_any_f32_bwd(dy, x, w, rstd):
     """dy fp32 -> (dx fp32, dw fp32 [dim])"""
     require_gpu(dy, x, w, rstd)
-    rows, dim = x.shape
-    assert dy.dtype == torch.float32 and dy.is_contiguous() and tuple(dy.shape) == (rows, dim)
-    dx = torch.empty_like(x)
-    dw = torch.empty(dim, device=x.device, dtype=torch.float32)
-    ws = _ws(lib().vt_rmsnorm_any_f32_bwd_workspace_bytes(dim), x.device)
-    check(lib().vt_rmsnorm_any_f32_bwd(ptr(dy), ptr(x), ptr(w), ptr(rstd), rows, dim, ptr(dx), ptr(dw), ptr(ws), stream()), "vt_rmsnorm_any_f32_bwd")
+    assert dy.dtype == torch.float32 and dy.is_contiguous() and tuple(dy.shape) == tuple(x.shape)
+    dx, _, dw = _rmsnorm_bwd("vt_rmsnorm_any_f32", dy, x, w, rstd)
     return dx, dw

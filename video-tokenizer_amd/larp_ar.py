@@ -27,6 +27,7 @@ import torch.nn.functional as F
 from . import hip
 from .embed import get_1d_sincos_pos_embed_from_grid
 from .functional import Linear as LinearFn
+from .functional import RMSNormRows
 from .pretrained import LocalPretrainedMixin
 from .registry import models as _registry
 
@@ -181,29 +182,9 @@ class _FfnBranch(torch.autograd.Function):
         return dx.reshape(B, L, D), dnw, dw31[I:].contiguous(), dw31[:I].contiguous(), dw2, None, None, None
 
 
-class _RMSNormFn(torch.autograd.Function):
-    """final RMSNorm in front of the output head (larp_ar.py:405); returns the bf16-rounded values in an fp32 tensor"""
-
-    @staticmethod
-    def forward(ctx, x, w, eps):
-        hip.require_gpu(x, w)
-        shp = x.shape
-        x2 = x.contiguous().reshape(-1, shp[-1]).float()
-        w = _f32(w)
-        y, rstd = hip.rmsnorm_fwd(x2, w, eps)
-        ctx.save_for_backward(x2, w, rstd)
-        return y.float().reshape(shp)
-
-    @staticmethod
-    def backward(ctx, dy):
-        x2, w, rstd = ctx.saved_tensors
-        dx, _, dw = hip.rmsnorm_bwd(hip.cast_rows(dy.contiguous().reshape(x2.shape).float()), x2, w, rstd)
-        return dx.reshape(dy.shape), dw, None
-
-
 # ------------------------------------------------------------------------------------------------ modules (the reference's tree)
 class RMSNorm(nn.Module):
-    """models/norm.py:6-17"""
+    """models/norm.py:6-17 on functional.RMSNormRows: returns the bf16-rounded values in an fp32 tensor"""
 
     def __init__(self, dim, eps=1e-5):
         super().__init__()
@@ -211,7 +192,7 @@ class RMSNorm(nn.Module):
         self.weight = nn.Parameter(torch.ones(dim))
 
     def forward(self, x):
-        return _RMSNormFn.apply(x, self.weight, self.eps)
+        return RMSNormRows.apply(x, self.weight, self.eps, "rmsnorm")
 
 
 class LabelEmbedder(nn.Module):
