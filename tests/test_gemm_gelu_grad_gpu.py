@@ -16,8 +16,8 @@ def hip():
     return h
 
 
-def _every_bf16_magnitude(M, K):
-    """[M, K] bf16: every exponent from 2^-40 to 2^20 in both signs, zeros, the GELU table's edge patterns, rows that stay inside the table
+def _every_bf16_magnitude_cpu(M, K):
+    """[M, K] bf16 on the CPU (tests/gated_cases.py builds its GEGLU gate half from it): every exponent from 2^-40 to 2^20 in both signs, zeros, the GELU table's edge patterns, rows that stay inside the table
     (the inputs of test_ops_gpu's GELU table test, restated)"""
     rng = np.random.default_rng(5)
     exps = rng.integers(-40, 21, size=(M, K))
@@ -28,7 +28,11 @@ def _every_bf16_magnitude(M, K):
     vals[2:6] = rng.normal(size=(4, K))          # rows that stay inside the table
     # (added to the restated inputs) the edges of the (gelu, gelu') pair table of the 192x192 kernel, |u| in [2^-12, 16)
     vals[6, :8] = [2.0 ** -12, -2.0 ** -12, 2.0 ** -13 * 1.9921875, -2.0 ** -13 * 1.9921875, 2.0 ** -12 * 1.0078125, 15.9375, 16.0, -16.0]
-    return torch.from_numpy(vals.astype(np.float32)).to(torch.bfloat16).cuda()
+    return torch.from_numpy(vals.astype(np.float32)).to(torch.bfloat16)
+
+
+def _every_bf16_magnitude(M, K):
+    return _every_bf16_magnitude_cpu(M, K).cuda()
 
 
 def _bits(t):
