@@ -249,6 +249,8 @@ int vt_attention_cross_bwd(const void* q, int64_t q_rs, const void* k, int64_t k
  * fp32 MFMA, cost independent of how the tokens spread over the codes); dW == NULL skips it (frozen codebook: the 'sq'
  * quantizer `VectorQuantizer` of models/model_new/quantizer/fsq.py:144-230, K = 196 560, which is vt_vq_forward mode 1 with
  * inv_tau = 1 and loss = d * loss_q).  `workspace`: vt_vq_workspace_bytes(N,K,d) bytes, the forward's scratch may be reused.
+ * N, K >= 1; every row stride given with a non-NULL buffer (ldp, ldg) is >= d.  Checked on the host: VT_ERR_INVALID + vt_last_error,
+ * nothing is launched.
  * ------------------------------------------------------------------------------------------ */
 size_t vt_vq_workspace_bytes(int32_t N, int32_t K, int32_t d);
 int vt_vq_forward(const float* z_in, int64_t ldz, const float* codebook, int32_t N, int32_t K, int32_t d, int32_t mode,

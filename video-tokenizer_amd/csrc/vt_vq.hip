@@ -470,6 +470,7 @@ extern "C" int vt_vq_forward(const float* z_in, int64_t ldz, const float* codebo
 extern "C" int vt_vq_gather(const float* E, const int64_t* idx, int32_t N, int32_t K, int32_t d, float* out, void* out_pad_bf16,
                             int64_t ldp, vtStream stream) {
     VT_CHECK_ARG(E && idx && (out || out_pad_bf16) && N > 0 && K > 0 && d > 0, "vt_vq_gather: bad arguments");
+    VT_CHECK_ARG(!out_pad_bf16 || ldp >= d, "vt_vq_gather: ldp < d");
     hipLaunchKernelGGL(vq_gather_kernel, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, E, idx, N, K, d, out, (bf16_t*)out_pad_bf16, ldp);
     VT_CHECK_LAUNCH("vt_vq_gather");
     return VT_OK;
@@ -492,6 +493,7 @@ extern "C" int vt_vq_backward(const float* g_rz, int64_t ldg, const float* gscal
                               void* workspace, vtStream stream) {
     VT_CHECK_ARG(zn && znorm && E && wnorm && idx && (dz_in || dz_pad_bf16) && workspace, "vt_vq_backward: null pointer");
     VT_CHECK_ARG(N > 0 && K > 0 && (d == 8 || d == 16 || d == 24 || d == 32), "vt_vq_backward: d=%d must be 8,16,24 or 32", d);
+    VT_CHECK_ARG((!dz_pad_bf16 || ldp >= d) && (!g_rz || ldg >= d), "vt_vq_backward: ldp < d or ldg < d");
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(vq_bwd_tokens_kernel, dim3((N + 255) / 256), dim3(256), 0, s, g_rz, ldg, gscal, beta, codebook_w, zn, znorm, E, idx, N, d, l2_normalized, dz_in, (bf16_t*)dz_pad_bf16, ldp);
     if (!dW) {   // frozen codebook (the 'sq' quantizer, model_new/quantizer/fsq.py:165-167): no codebook gradient, 2NKd flops saved
