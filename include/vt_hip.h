@@ -88,12 +88,13 @@ typedef struct {
     int32_t tile;                            /* tile generation for THIS call: 0 = automatic (use this; 192x192x64 tiles on a
                                                 3-stage LDS-DMA ring, one persistent workgroup per CU, when the problem fills
                                                 them, else 128x128x64).  Tests / tuning: 1 = force 128 (2-deep ring), 16 = force 128
-                                                (4-deep ring), 2 = force 192, 5 = 192x96 two workgroups per CU, 6 = 192x192 one tile per
+                                                (4-deep ring), 2 = force 192, 6 = 192x192 one tile per
                                                 workgroup, 7 = the M <= 64 weight-streaming kernel, 19 = 192x192 walking its tiles as a
                                                 row-major list, 19 + W (W = 1..12) = in column blocks of W tile columns (A/B timing of the
                                                 order, same results).  Every other value is VT_ERR_INVALID: 3, 4, 8..15, 17 and 18 once
-                                                selected timing experiments inside the 192x192 kernel (some with wrong results on purpose);
-                                                they are gone, and no caller passed them.  Results do not depend on the choice (same fp32
+                                                selected timing experiments inside the 192x192 kernel (some with wrong results on purpose)
+                                                and 5 a 192x96 instantiation that no dispatch rule picked; they are gone, and no caller
+                                                passed them.  Results do not depend on the choice (same fp32
                                                 summation order) unless K is split, below.  The library keeps no such setting between calls.
                                                 Automatic tile order of both NT kernels (vt_auto_col_block): column blocks of the width
                                                 nearest the square root of the tiles one XCD has in flight, the tile columns cut into

@@ -83,7 +83,7 @@ MULAUX_SHAPES = [(384, 384, 128), (200, 196, 128), (100, 64, 64)]
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("tile", [1, 2, 5, 6], ids=["tile128", "tile192", "tile192x96", "tile192_one_tile_per_wg"])
+@pytest.mark.parametrize("tile", [1, 2, 6], ids=["tile128", "tile192", "tile192_one_tile_per_wg"])
 @pytest.mark.parametrize("M,N,K", MULAUX_SHAPES)
 def test_mulaux_is_an_exact_restatement(hip, M, N, K, tile):
     """out = bf16(h * aux) with h what EPI_BF16 writes: the fp32 product of two bf16 values is exact, so the restatement in torch is
@@ -108,6 +108,58 @@ def test_mulaux_is_an_exact_restatement(hip, M, N, K, tile):
         if not sign_free:
             want = torch.stack([out[t * 192:(t + 1) * 192].double().sum(0) for t in range(slabs)])
             np.testing.assert_allclose(part.double().cpu().numpy(), want.cpu().numpy(), rtol=1e-5, atol=0)
+
+
+# N, ldo, ldo2 and the read-back width of the 192x192 kernel that they select (16 bytes per lane needs N, ldo and -- where there is an
+# out2 -- ldo2 to be multiples of 8; each of the three alone sends the launch to 8 bytes per lane)
+READ_BACK_CASES = [(192, 192, 192, "16 bytes"), (196, 196, 196, "8 bytes through N"), (192, 196, 192, "8 bytes through ldo"),
+                   (192, 192, 196, "8 bytes through ldo2")]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("K", [64, 256], ids=["one_k_tile", "four_k_tiles_ring_wraps"])
+@pytest.mark.parametrize("M", [192, 200])
+def test_read_back_width_dispatch_of_the_192_tile_kernel(hip, M, K):
+    """The 192x192 kernel reads its staged bf16 image back 16 or 8 bytes per lane, chosen per launch from N, ldo and ldo2.  For every
+    epilogue that takes this read-back, persistent (tile 2) and one tile per workgroup (tile 6): each output equals the 128x128 kernel's
+    (tile 1) on the same operands -- the same summation order and the same per-element arithmetic, so bit for bit, no tolerance -- and
+    every element of the destination buffers outside [0, M) x [0, N) still holds the bit pattern the buffer was filled with (the
+    buffers are two tiles of rows deep, so a store past M or N would land in them).
+    What this does not see: WHICH width a launch took (the hardware accepts a 16-byte store at an 8-byte-aligned address, and the 8-byte
+    walk is right for every launch), and the per-element arithmetic on its own (tile 1 calls the same epi_values; the other tests of
+    this file hold it to fp64 and to exact restatements).  Checked here, independently of tile 1: the walk over the staged image and the
+    stores, in both widths' code, at the shapes that select each."""
+    sentinel = 0x7FC5                                   # a NaN no kernel produces
+    depth = 392
+
+    def buffer(ld):
+        b = torch.empty(depth, ld, dtype=torch.bfloat16, device="cuda")
+        _bits(b).fill_(sentinel)
+        return b
+
+    for N, ldo, ldo2, what in READ_BACK_CASES:
+        A, B, aux = _rand_bf16((M, K), 41, 0.5), _rand_bf16((N, K), 42, 0.5), _rand_bf16((M, N), 43)
+        bias = torch.randn(N, generator=torch.Generator().manual_seed(44)).cuda()
+        for epi in (hip.EPI_BF16, hip.EPI_BF16_GELU, hip.EPI_BF16_GELU_GRAD, hip.EPI_BF16_MULAUX):
+            two = epi in (hip.EPI_BF16_GELU, hip.EPI_BF16_GELU_GRAD)
+            if what.endswith("ldo2") and not two:
+                continue                                # no out2: the same launch as the first case
+
+            def run(tile):
+                bufs = [buffer(ldo)] + ([buffer(ldo2)] if two else [])
+                hip.gemm_nt(A, B, epi=epi, bias=bias, aux=aux if epi == hip.EPI_BF16_MULAUX else None, out=bufs[0][:M, :N],
+                            out2=bufs[1][:M, :N] if two else None, tile=tile, splitk=1)
+                return bufs
+
+            want = run(1)
+            for tile in (2, 6):
+                got = run(tile)
+                torch.cuda.synchronize()
+                for g, w in zip(got, want):
+                    where = (what, epi, tile, M, K)
+                    assert torch.equal(g[:M, :N], w[:M, :N]), where
+                    assert torch.equal(_bits(g)[:M, :N], _bits(w)[:M, :N]), where
+                    assert bool((_bits(g)[M:] == sentinel).all()) and bool((_bits(g)[:M, N:] == sentinel).all()), where
 
 
 @pytest.mark.gpu

@@ -330,7 +330,7 @@ def test_c_abi_exports_every_declared_symbol():
 
 
 def test_gemm_nt_rejects_the_removed_tile_values():
-    """vtGemmNT.tile 3, 4, 8..15, 17 and 18 selected timing experiments that are gone: with otherwise valid arguments they are refused by the
+    """vtGemmNT.tile 3, 4, 8..15, 17 and 18 selected timing experiments, and 5 a 192x96 instantiation, that are gone: with otherwise valid arguments they are refused by the
     host-side validation (no launch, no GPU), and the message names the field."""
     lib = vt.hip.lib()
     p = vt.hip.GemmNT()
@@ -338,7 +338,7 @@ def test_gemm_nt_rejects_the_removed_tile_values():
     p.M, p.N, p.K, p.lda, p.ldb, p.ldo = 192, 192, 64, 64, 64, 192
     p.epi, p.splitk = vt.hip.EPI_BF16, 1
     buf = ctypes.create_string_buffer(512)
-    for tile in (3, 4, 8, 15, 17, 18):
+    for tile in (3, 4, 5, 8, 15, 17, 18):
         p.tile = tile
         assert lib.vt_gemm_nt(ctypes.byref(p), None) == -1, tile
         lib.vt_last_error(buf, 512)

@@ -35,7 +35,7 @@ def rel(a, b):
 
 
 # ------------------------------------------------------------------------------------------- GEMM
-@pytest.fixture(params=[1, 2, 5, 6], ids=["tile128", "tile192", "tile192x96", "tile192_one_tile_per_wg"], autouse=False)
+@pytest.fixture(params=[1, 2, 6], ids=["tile128", "tile192", "tile192_one_tile_per_wg"], autouse=False)
 def gemm_variant(request, hip):
     """run a GEMM test once per tile generation (hip.GEMM_TILE -> vtGemmNT.tile), then restore auto dispatch"""
     hip.GEMM_TILE = request.param
@@ -681,7 +681,7 @@ def test_vq_stochastic_mode_matches_softmax_distribution(hip):
     assert (o3["idx"][perm] != o["idx"]).float().mean() > 0.5
 
 
-@pytest.mark.parametrize("M,N,K,variant", [(200, 320, 128, 2), (700, 768, 192, 2), (400, 96, 64, 5)])
+@pytest.mark.parametrize("M,N,K,variant", [(200, 320, 128, 2), (700, 768, 192, 2), (400, 96, 64, 2)])
 def test_gemm_nt_dgelu_fused_column_sums(hip, M, N, K, variant):
     """vtGemmNT.colsum_partial: per-192-row column sums of the rounded output, out of the epilogue (fc1 bias gradient)"""
     hip.GEMM_TILE = variant

@@ -21,7 +21,7 @@ def traffic(raw, out, note):
                     "traffic_bytes": t, "algorithmic_bytes": a, "ratio": round(t / a, 3)})
         tb.append(t)
         ab.append(a)
-    json.dump({"kernel": "gemm_nt192_kernel<VT_EPI_BF16, 4>", "tool": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, --kernel-trace), tools/pmc_traffic.sh; " + note,
+    json.dump({"kernel": "gemm_nt192_kernel<VT_EPI_BF16>", "tool": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, --kernel-trace), tools/pmc_traffic.sh; " + note,
                "correction": "bytes = (2*FETCH_SIZE + WRITE_SIZE)*1024: on gfx950 FETCH_SIZE tallies 128-B requests as 64 B (MI355X_MICROARCH.md section HBM); counters are L2 fabric requests, Infinity-Cache hits included",
                "per_shape": per, "traffic_bytes_per_launch_mean": sum(tb) / len(tb), "algorithmic_bytes_per_launch_mean": sum(ab) / len(ab),
                "ratio_mean": round(sum(tb) / sum(ab), 3)}, open(out, "w"), indent=1)

@@ -279,7 +279,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(const NTArgs a) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const f32x4 v = acc[i][j] + b4[j];
-                    *(bf16x4*)(smem + (wr * 64 + i * 16 + fr) * STRIDE + (wc * 16 + j * 4 + fq) * 8) = (bf16x4){f2bf(v[0]), f2bf(v[1]), f2bf(v[2]), f2bf(v[3])};
+                    *(bf16x4*)(smem + (wr * 64 + i * 16 + fr) * STRIDE + (wc * 16 + j * 4 + fq) * 8) = f2bf4(v);
                 }
             __syncthreads();
 #pragma unroll 2
@@ -289,25 +289,11 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(const NTArgs a) {
                 const int m = m0 + row, n = n0 + c * 4;
                 if (m >= p.M || n >= p.N) continue;
                 const bf16x4 h = *(const bf16x4*)(smem + row * STRIDE + c * 8);
-                bf16_t* o = (bf16_t*)p.out + (int64_t)m * p.ldo + n;
-                if constexpr (EPI == VT_EPI_BF16) {
-                    st_stream((bf16x4*)o, h);
-                } else if constexpr (EPI == VT_EPI_BF16_GELU) {
-                    st_stream((bf16x4*)o, h);
-                    st_stream((bf16x4*)((bf16_t*)p.out2 + (int64_t)m * p.ldo2 + n),
-                              (bf16x4){f2bf(gelu_erf(bf2f(h[0]))), f2bf(gelu_erf(bf2f(h[1]))), f2bf(gelu_erf(bf2f(h[2]))), f2bf(gelu_erf(bf2f(h[3])))});
-                } else if constexpr (EPI == VT_EPI_BF16_GELU_GRAD) {
-                    bf16x4 g, dg;
-                    gelu_and_grad4(h, g, dg);
-                    st_stream((bf16x4*)o, dg);
-                    st_stream((bf16x4*)((bf16_t*)p.out2 + (int64_t)m * p.ldo2 + n), g);
-                } else if constexpr (EPI == VT_EPI_BF16_MULAUX) {
-                    st_stream((bf16x4*)o, mul_aux4(h, ld_stream((const bf16x4*)((const bf16_t*)p.aux + (int64_t)m * p.ldaux + n))));
-                } else {
-                    const bf16x4 uu = ld_stream((const bf16x4*)((const bf16_t*)p.aux + (int64_t)m * p.ldaux + n));
-                    st_stream((bf16x4*)o, (bf16x4){f2bf(bf2f(h[0]) * gelu_erf_grad(bf2f(uu[0]))), f2bf(bf2f(h[1]) * gelu_erf_grad(bf2f(uu[1]))),
-                                                   f2bf(bf2f(h[2]) * gelu_erf_grad(bf2f(uu[2]))), f2bf(bf2f(h[3]) * gelu_erf_grad(bf2f(uu[3])))});
-                }
+                bf16x4 aux = h, out, out2;   // (aux: read by the two epilogues that have one)
+                if constexpr (epi_has_aux(EPI)) aux = ld_stream((const bf16x4*)((const bf16_t*)p.aux + (int64_t)m * p.ldaux + n));
+                epi_values<EPI, 4>(h, aux, out, out2);
+                st_stream((bf16x4*)((bf16_t*)p.out + (int64_t)m * p.ldo + n), out);
+                if constexpr (epi_has_out2(EPI)) st_stream((bf16x4*)((bf16_t*)p.out2 + (int64_t)m * p.ldo2 + n), out2);
             }
         } else {
             constexpr int FSTRIDE = BN * 4 + 16;  // fp32 image of 64 rows (one wave row) at a time
@@ -337,7 +323,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(const NTArgs a) {
                     if (p.rowmod) v += *(const f32x4*)(p.rowmod + (int64_t)(m % p.rowmod_period) * p.N + n);
                     if (p.out_scale != 0.f) v *= p.out_scale;
                     *(f32x4*)((float*)p.out + orow * p.ldo + n) = v;
-                    if (p.out2) st_stream((bf16x4*)((bf16_t*)p.out2 + orow * p.ldo2 + n), (bf16x4){f2bf(v[0]), f2bf(v[1]), f2bf(v[2]), f2bf(v[3])});
+                    if (p.out2) st_stream((bf16x4*)((bf16_t*)p.out2 + orow * p.ldo2 + n), f2bf4(v));
                 }
             }
         }
@@ -533,7 +519,7 @@ constexpr int VT_SPLITK_CTR_BYTES = 4096;   // arrival counters (one per 128x128
 extern "C" size_t vt_gemm_nt_splitk_workspace_bytes(void) { return VT_SPLITK_CTR_BYTES + (size_t)512 * BM * BN * 4; }   // automatic rule: tiles x split <= 2 x 256
 
 // vt_gemm192.hip
-int vt_gemm_nt192_launch(const vtGemmNT& p, hipStream_t s, int half, int one_tile, int order);
+int vt_gemm_nt192_launch(const vtGemmNT& p, hipStream_t s, int one_tile, int order);
 int vt_gemm_tn192_launch(const vtGemmTN* ph, int n, hipStream_t s, int burst);
 int vt_gemm192_init();
 int vt_gemm_num_cus();
@@ -541,7 +527,7 @@ int vt_gemm_col_block(int forced, int tiles_n, int nwg, int wg_per_cu);
 
 // What a value of vtGemmNT.tile asks for
 struct NTTile {
-    enum Kernel { AUTO, SKINNY, T128_RING2, T128_RING4, T192, T192X96 } kernel;
+    enum Kernel { AUTO, SKINNY, T128_RING2, T128_RING4, T192 } kernel;
     bool one_tile;   // 192x192 only: one tile per workgroup instead of the persistent walk
     int order;       // 192x192 only: forced tile order (0 = row-major list, W = column blocks of W tile columns), -1 = automatic
 };
@@ -551,7 +537,6 @@ static bool decode_nt_tile(int tile, NTTile& t) {
         case 0: return true;
         case 1: t.kernel = NTTile::T128_RING2; return true;
         case 2: t.kernel = NTTile::T192; return true;
-        case 5: t.kernel = NTTile::T192X96; return true;
         case 6: t.kernel = NTTile::T192; t.one_tile = true; return true;
         case 7: t.kernel = NTTile::SKINNY; return true;
         case 16: t.kernel = NTTile::T128_RING4; return true;
@@ -566,7 +551,7 @@ extern "C" int vt_gemm_nt(const vtGemmNT* ph, vtStream stream) {
     const vtGemmNT& p = *ph;
     VT_CHECK_ARG(p.A && p.B && p.out, "vt_gemm_nt: null operand");
     NTTile tile;   // per call (vtGemmNT.tile); the library holds no tile setting of its own
-    VT_CHECK_ARG(decode_nt_tile(p.tile, tile), "vt_gemm_nt: tile %d (0 auto, 1 = 128x128 2-deep ring, 16 = 128x128 4-deep ring, 2 = 192x192, 5 = 192x96, 6 = 192x192 one tile per workgroup, 7 = skinny M <= 64, 19..31 = tile order of the 192x192 kernel)", p.tile);
+    VT_CHECK_ARG(decode_nt_tile(p.tile, tile), "vt_gemm_nt: tile %d (0 auto, 1 = 128x128 2-deep ring, 16 = 128x128 4-deep ring, 2 = 192x192, 6 = 192x192 one tile per workgroup, 7 = skinny M <= 64, 19..31 = tile order of the 192x192 kernel)", p.tile);
     VT_CHECK_ARG(p.M > 0 && p.N > 0 && p.K > 0 && p.K % BK == 0, "vt_gemm_nt: K=%d must be a positive multiple of 64 (M=%d N=%d)", p.K, p.M, p.N);
     VT_CHECK_ARG(p.lda % 8 == 0 && p.ldb % 8 == 0 && p.lda >= p.K && p.ldb >= p.K, "vt_gemm_nt: lda/ldb must be >= K and multiples of 8");
     VT_CHECK_ARG(((uintptr_t)p.A & 15) == 0 && ((uintptr_t)p.B & 15) == 0, "vt_gemm_nt: A/B must be 16-byte aligned");
@@ -601,7 +586,7 @@ extern "C" int vt_gemm_nt(const vtGemmNT* ph, vtStream stream) {
         VT_CHECK_LAUNCH("vt_gemm_nt(skinny)");
         return VT_OK;
     }
-    bool big = tile.kernel == NTTile::T192 || tile.kernel == NTTile::T192X96 || p.colsum_partial;
+    bool big = tile.kernel == NTTile::T192 || p.colsum_partial;
     if (tile.kernel == NTTile::AUTO && !big && p.N >= 192 && p.M >= 192) {
         // cost in units of one full round of 192x192 tiles (256 workgroups, one per CU).  A partly filled last round of
         // that kernel costs a whole round; the 128x128 kernel runs two workgroups per CU (512 per round, a round ~1.05 of
@@ -617,7 +602,7 @@ extern "C" int vt_gemm_nt(const vtGemmNT* ph, vtStream stream) {
     }
     if (big) {
         TRY(vt_gemm192_init());
-        TRY(vt_gemm_nt192_launch(p, (hipStream_t)stream, tile.kernel == NTTile::T192X96, tile.one_tile, tile.order));
+        TRY(vt_gemm_nt192_launch(p, (hipStream_t)stream, tile.one_tile, tile.order));
         VT_CHECK_LAUNCH("vt_gemm_nt(192)");
         return VT_OK;
     }

@@ -23,8 +23,11 @@ constexpr int TM = 192, TN_ = 192, TK = 64;
 constexpr int OP_BYTES = TM * TK * 2;      // 24 KiB per operand tile (both layouts)
 constexpr int STAGE_BYTES = 2 * OP_BYTES;  // A | B
 constexpr int NSTAGE = 3;
+constexpr int THREADS = 512;               // 8 waves as 2 (M) x 4 (N)
+constexpr int PA = 3, PB = 3, P = PA + PB; // 16-B DMA pieces per thread per K-tile: A rows, B rows
 
-__device__ __forceinline__ void wait_vmcnt6() { asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); }
+__device__ __forceinline__ void wait_vmcnt6() { asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); }   // = vmcnt(P): one K-tile's pieces stay in flight
+static_assert(P == 6 && PA * THREADS == TM * 8 && PB * THREADS == TN_ * 8, "wait_vmcnt6 counts one K-tile");
 __device__ __forceinline__ void wait_vmcnt0() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 __device__ __forceinline__ void raw_barrier() {
     asm volatile("" ::: "memory");
@@ -36,28 +39,7 @@ __device__ __forceinline__ void raw_barrier() {
 struct NT192Args {
     vtGemmNT p;
     int tiles_m, tiles_n;
-    int col_block;  // tile order: 0 = row-major list, W > 0 = column blocks of W tile columns, row-major inside a block (launch_nt192)
-};
-
-// Geometry of the two NT instantiations.  WN = waves along N (each wave owns 96 x 48 outputs):
-//   WN = 4: 512 threads, 192 x 192 tile, 3-stage ring (144 KiB)  -> one workgroup per CU
-//   WN = 2: 256 threads, 192 x  96 tile, 2-stage ring ( 72 KiB)  -> two workgroups per CU.  Measured (tools/
-//           gemm_half_bench.py): within 0-8 % BEHIND the 192x192 kernel on every training shape.  Co-resident
-//           workgroups start together and stay in phase (the dispatcher puts blocks b and b+256 on one CU,
-//           tools/probes/placement_probe.hip), so their epilogues do not fall into each other's main loops, and a
-//           forced start offset cost more than it recovered.  Kept as a tile option (vtGemmNT.tile = 5) and as
-//           the record of that experiment; auto dispatch never picks it.
-template <int WN>
-struct NTGeo {
-    static constexpr int THREADS = 128 * WN;
-    static constexpr int TNW = 48 * WN;               // tile extent along N
-    static constexpr int OPA = TM * TK * 2;           // A image bytes
-    static constexpr int OPB = TNW * TK * 2;          // B image bytes
-    static constexpr int STAGE = OPA + OPB;
-    static constexpr int NST = WN == 4 ? 3 : 2;
-    static constexpr int PA = TM * 8 / THREADS;       // 16-B DMA pieces per thread per K-tile, A rows
-    static constexpr int PB = TNW * 8 / THREADS;      // ... B rows
-    static constexpr int P = PA + PB;
+    int col_block;  // tile order: 0 = row-major list, W > 0 = column blocks of W tile columns, row-major inside a block (vt_gemm_nt192_launch)
 };
 
 // gelu(u) of the fc1 epilogue by table.  It is applied to a value that is ALREADY bf16 (the rounded pre-activation u), so it is
@@ -92,64 +74,92 @@ struct GeluTab {
 };
 __device__ __forceinline__ unsigned bf16_bits(bf16_t x) { return (unsigned)__builtin_bit_cast(unsigned short, x); }
 __device__ __forceinline__ bf16_t bf16_from_bits(unsigned b) { return __builtin_bit_cast(bf16_t, (unsigned short)b); }
-template <int N>
-using bf16xN = __bf16 __attribute__((ext_vector_type(N)));
-// gelu of the N bf16 values a lane read back.  TABLE: from the table at `tab`, unless some lane of the wave holds a value outside its range --
+// gelu of the N bf16 values a lane read back: from the table at `tab`, unless some lane of the wave holds a value outside its range --
 // then the whole wave takes the arithmetic (wave-uniform branch; the same bits either way).
-template <int N, bool TABLE>
+template <int N>
 __device__ __forceinline__ bf16xN<N> gelu_lookup(const bf16xN<N>& h, const bf16_t* tab) {
-    bf16xN<N> gl;
-    if constexpr (TABLE) {
-        unsigned idx[N], any = 0;
+    bf16xN<N> gl, u;
+    unsigned idx[N], any = 0;
 #pragma unroll
-        for (int e = 0; e < N; ++e) { idx[e] = GeluTab<VT_EPI_BF16_GELU>::index(bf16_bits(h[e])); any |= idx[e]; }
-        if (__builtin_amdgcn_ballot_w64((any & 0x8000u) != 0) == 0) {
+    for (int e = 0; e < N; ++e) { idx[e] = GeluTab<VT_EPI_BF16_GELU>::index(bf16_bits(h[e])); any |= idx[e]; }
+    if (__builtin_amdgcn_ballot_w64((any & 0x8000u) != 0) == 0) {
 #pragma unroll
-            for (int e = 0; e < N; ++e) gl[e] = tab[idx[e]];
-            return gl;
-        }
+        for (int e = 0; e < N; ++e) gl[e] = tab[idx[e]];
+        return gl;
     }
-#pragma unroll
-    for (int e = 0; e < N; ++e) gl[e] = f2bf(gelu_erf(bf2f(h[e])));
+    epi_values<VT_EPI_BF16_GELU, N>(h, h, u, gl);
     return gl;
 }
 // gelu (g) and gelu' (dg) of the N bf16 values a lane read back, for VT_EPI_BF16_GELU_GRAD: one 4-byte table entry per value, or one
 // gelu_parts evaluation per value for the whole wave when some lane is outside the table (the same bits either way)
-template <int N, bool TABLE>
+template <int N>
 __device__ __forceinline__ void gelu_grad_lookup(const bf16xN<N>& h, const char* tab, bf16xN<N>& g, bf16xN<N>& dg) {
     using GT = GeluTab<VT_EPI_BF16_GELU_GRAD>;
-    if constexpr (TABLE) {
-        unsigned idx[N], any = 0;
+    unsigned idx[N], any = 0;
 #pragma unroll
-        for (int e = 0; e < N; ++e) { idx[e] = GT::index(bf16_bits(h[e])); any |= idx[e]; }
-        if (__builtin_amdgcn_ballot_w64((any & 0x8000u) != 0) == 0) {
+    for (int e = 0; e < N; ++e) { idx[e] = GT::index(bf16_bits(h[e])); any |= idx[e]; }
+    if (__builtin_amdgcn_ballot_w64((any & 0x8000u) != 0) == 0) {
 #pragma unroll
-            for (int e = 0; e < N; ++e) {
-                const unsigned w = ((const unsigned*)tab)[idx[e]];
-                g[e] = bf16_from_bits(w & 0xFFFFu), dg[e] = bf16_from_bits(w >> 16);
-            }
-            return;
+        for (int e = 0; e < N; ++e) {
+            const unsigned w = ((const unsigned*)tab)[idx[e]];
+            g[e] = bf16_from_bits(w & 0xFFFFu), dg[e] = bf16_from_bits(w >> 16);
         }
+        return;
     }
+    epi_values<VT_EPI_BF16_GELU_GRAD, N>(h, h, dg, g);
+}
+
+// Read-back of the [192][192] bf16 image that the epilogue staged at `img` (rows of IMG_STRIDE bytes), VEC bf16 per lane: 64 / VEC lanes
+// cover a 64-column group of a row (whole 128-byte lines per wave instruction), THREADS / (64 / VEC) rows go per pass, and a pass is one
+// batch of 3 image reads -- the row's three column groups -- followed by their stores: with one read in flight per store (the compiler's
+// order for the plain loop) every store waits a full LDS round trip.  Every address is one per-thread base plus compile-time terms.
+//   VEC = 8 (round 4): two 8-byte image reads (rows are only 8-byte aligned) and ONE global_store_dwordx4, a wave instruction writes 1 KiB.
+//            8-byte accesses run at 0.54-0.70 of the 16-byte rate (MI355X_MICROARCH, visibility table) and the epilogue is what a round of
+//            this kernel pays outside its main loop (6-13 us, all 256 CUs storing at once).  Needs 8-column alignment of every output.
+//   VEC = 4: the same walk for outputs that are only 4-column aligned.
+constexpr int IMG_STRIDE = TN_ * 2 + 8;   // +8 B: the 16 rows of a ds_write_b64 group fall on 16 different bank pairs
+template <int EPI, int VEC>
+__device__ __forceinline__ void nt192_read_back(const vtGemmNT& p, const char* img, const char* tab, unsigned tid, int m0, int n0) {
+    using V = bf16xN<VEC>;
+    constexpr int LPG = 64 / VEC, RPP = THREADS / LPG;   // lanes per column group, rows per pass
+    const int col0 = (tid % LPG) * VEC;
+#pragma unroll 1
+    for (int row = tid / LPG; row < TM; row += RPP) {
+        V hh[3];
 #pragma unroll
-    for (int e = 0; e < N; ++e) {
-        float gf, df;
-        gelu_erf_and_grad(bf2f(h[e]), gf, df);
-        g[e] = f2bf(gf), dg[e] = f2bf(df);
+        for (int g = 0; g < 3; ++g) {
+            const char* src = img + row * IMG_STRIDE + (col0 + g * 64) * 2;
+            if constexpr (VEC == 8) hh[g] = cat4(*(const bf16x4*)src, *(const bf16x4*)(src + 8));
+            else hh[g] = *(const bf16x4*)src;
+        }
+#pragma unroll
+        for (int g = 0; g < 3; ++g) {
+            const int m = m0 + row, n = n0 + col0 + g * 64;
+            if (m >= p.M || n >= p.N) continue;
+            V* const o = (V*)((bf16_t*)p.out + (int64_t)m * p.ldo + n);
+            auto o2 = [&] { return (V*)((bf16_t*)p.out2 + (int64_t)m * p.ldo2 + n); };   // (only the epilogues that have an out2 form it)
+            if constexpr (EPI == VT_EPI_BF16_GELU_GRAD) {   // out = gelu'(u), out2 = gelu(u)
+                V gl, dg;
+                gelu_grad_lookup<VEC>(hh[g], tab, gl, dg);
+                st_stream_any(o, dg);
+                st_stream_any(o2(), gl);
+            } else {
+                st_stream_any(o, hh[g]);
+                if constexpr (EPI == VT_EPI_BF16_GELU) st_stream_any(o2(), gelu_lookup<VEC>(hh[g], (const bf16_t*)tab));
+            }
+        }
     }
 }
 
 // The P 16-B-per-lane DMA pieces of a K-tile (pieces 0..PA-1 = A rows, PA..P-1 = B rows).  A lane's byte offset inside
 // its operand's [tile rows][K] panel does not depend on the K-tile (row clamp and swizzle are per row), so it is computed
 // once (nt192_piece_offsets) and every K-tile costs only the scalar advance of the two panel pointers: glds16_sv.
-template <int WN>
-__device__ __forceinline__ void nt192_piece_offsets(int64_t lda, int m0, int M, int64_t ldb, int n0, int N, int tid, unsigned (&off)[NTGeo<WN>::P]) {
-    using G = NTGeo<WN>;
+__device__ __forceinline__ void nt192_piece_offsets(int64_t lda, int m0, int M, int64_t ldb, int n0, int N, int tid, unsigned (&off)[P]) {
 #pragma unroll
-    for (int piece = 0; piece < G::P; ++piece) {
-        const bool isA = piece < G::PA;
-        const int i = isA ? piece : piece - G::PA;
-        const int slot = i * G::THREADS + tid;
+    for (int piece = 0; piece < P; ++piece) {
+        const bool isA = piece < PA;
+        const int i = isA ? piece : piece - PA;
+        const int slot = i * THREADS + tid;
         const int row = slot >> 3;
         const int lc = (slot & 7) ^ ((row >> 1) & 7);
         const int r0 = isA ? m0 : n0, lim = isA ? M : N;
@@ -158,34 +168,30 @@ __device__ __forceinline__ void nt192_piece_offsets(int64_t lda, int m0, int M, 
         off[piece] = (unsigned)((gr * (isA ? lda : ldb) + lc * 8) * 2);
     }
 }
-template <int WN>
-__device__ __forceinline__ void nt192_stage_piece(const bf16_t* a_panel, const bf16_t* b_panel, const unsigned (&off)[NTGeo<WN>::P], unsigned lds,
+__device__ __forceinline__ void nt192_stage_piece(const bf16_t* a_panel, const bf16_t* b_panel, const unsigned (&off)[P], unsigned lds,
                                                   int piece, int wave) {
-    using G = NTGeo<WN>;
-    const bool isA = piece < G::PA;
-    const int i = isA ? piece : piece - G::PA;
-    glds16_sv(isA ? a_panel : b_panel, off[piece], lds + (isA ? 0 : G::OPA) + (i * G::THREADS + wave * 64) * 16);
+    const bool isA = piece < PA;
+    const int i = isA ? piece : piece - PA;
+    glds16_sv(isA ? a_panel : b_panel, off[piece], lds + (isA ? 0 : OP_BYTES) + (i * THREADS + wave * 64) * 16);
 }
 
-template <int EPI, int WN>
-__global__ __launch_bounds__(128 * WN, 2) void gemm_nt192_kernel(const NT192Args a) {
-    using G = NTGeo<WN>;
+template <int EPI>
+__global__ __launch_bounds__(THREADS, 2) void gemm_nt192_kernel(const NT192Args a) {
     extern __shared__ __attribute__((aligned(128))) char smem[];
     const vtGemmNT& p = a.p;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave / WN, wn = wave % WN;
+    const int wm = wave >> 2, wn = wave & 3;
 
     const int nwg = a.tiles_m * a.tiles_n;
     const bf16_t* A = (const bf16_t*)p.A;
     const bf16_t* B = (const bf16_t*)p.B;
-    // Ring slot of K-tile t.  The 3-stage kernel is persistent (grid = min(tiles, CUs), workgroup b walks tiles b, b + grid,
+    // Ring slot of K-tile t.  The kernel is persistent (grid = min(tiles, CUs), workgroup b walks tiles b, b + grid,
     // ...): K-tile 0 of the NEXT output tile is DMA-ed into slot 2 before the epilogue of the current one -- the staged
     // epilogue image lives in slots 0-1 -- so its HBM latency runs under the epilogue's stores instead of in front of the
     // first MFMA (tools/gemm_epilogue_cost.py: ~3 us of the 6-20 us a tile pays outside its main loop).
-    constexpr int ROT = G::NST == 3 ? 2 : 0;
-    auto slot_of = [](int t) { return (t + ROT) % G::NST; };
+    auto slot_of = [](int t) { return (t + 2) % NSTAGE; };
 
     const int nt = p.K / TK;
     const unsigned sbase = __builtin_amdgcn_readfirstlane(lds_addr_of(smem));
@@ -197,12 +203,12 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm_nt192_kernel(const NT192Args
     // k-step 1 is chunk 4 + fq: (4 + fq) ^ s = (fq ^ s) ^ 4, i.e. the k-step-0 ADDRESS with bit 6 flipped (ring slots and operand images are
     // multiples of 128 bytes) -- formed per K-tile from the k-step-0 address, so only two lane offsets live across the main loop.
     const unsigned a_off0 = arow * 128 + ((fq ^ ((arow >> 1) & 7)) << 4);
-    const unsigned b_off0 = G::OPA + brow * 128 + ((fq ^ ((brow >> 1) & 7)) << 4);
-    static_assert(G::OPA % 128 == 0 && G::STAGE % 128 == 0, "k-step 1 = k-step 0 ^ 64");
+    const unsigned b_off0 = OP_BYTES + brow * 128 + ((fq ^ ((brow >> 1) & 7)) << 4);
+    static_assert(OP_BYTES % 128 == 0 && STAGE_BYTES % 128 == 0, "k-step 1 = k-step 0 ^ 64");
 
     // ---- software pipeline across K-tiles -------------------------------------------------------------------------
     // Tile t is multiplied out of a REGISTER set while the 18 fragment reads of tile t+1 are issued between its MFMA
-    // rows into the other set, and the LDS-DMA of tile t+NST is in flight into the LDS buffer tile t just vacated.
+    // rows into the other set, and the LDS-DMA of tile t+NSTAGE is in flight into the LDS buffer tile t just vacated.
     // (Without this, all 8 waves burst-read 144 KB of fragments after every barrier before any MFMA can issue: an
     // ablation with the DMA removed still ran at 88 % of the full kernel's time.)  Reads and DMAs are inline asm, so
     // every wait is explicit: vmcnt counts this thread's P DMA pieces per tile, lgkmcnt(0) closes a tile's reads
@@ -218,7 +224,7 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm_nt192_kernel(const NT192Args
     if (dma_tile >= 0) {                                                                                             \
         const bf16_t* ap_ = Apanel + dma_tile * TK;                                                                  \
         const bf16_t* bp_ = Bpanel + dma_tile * TK;                                                                  \
-        _Pragma("unroll") for (int k_ = 0; k_ < G::P; ++k_) nt192_stage_piece<WN>(ap_, bp_, poff, dma_dst, k_, wave); \
+        _Pragma("unroll") for (int k_ = 0; k_ < P; ++k_) nt192_stage_piece(ap_, bp_, poff, dma_dst, k_, wave); \
     }
 #define VT_STEP(Ca0, Cb0, Ca1, Cb1, Na0, Nb0, Na1, Nb1, nb, pf)                                                      \
     {                                                                                                                \
@@ -251,7 +257,7 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm_nt192_kernel(const NT192Args
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                           \
         __builtin_amdgcn_sched_barrier(0);                                                                           \
     }
-    unsigned poff[G::P];
+    unsigned poff[P];
     const bf16_t *Apanel, *Bpanel;   // wave-uniform: rows m0.. of A / n0.. of B, K-tile 0
     int m0, n0;
     bool poff_full = false;          // poff holds the offsets of a tile that lies fully inside the matrix (no row is clamped): the same for every such tile
@@ -259,28 +265,28 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm_nt192_kernel(const NT192Args
         const int sid = xcd_remap(it, nwg);
         int tm, tn;   // an XCD's contiguous chunk of the list is a rectangle of tiles: fewer distinct operand panels among the tiles in flight on its L2
         vt_tile_of(sid, a.tiles_m, a.tiles_n, a.col_block, tm, tn);
-        m0 = __builtin_amdgcn_readfirstlane(tm) * TM, n0 = __builtin_amdgcn_readfirstlane(tn) * G::TNW;
-        const bool full = m0 + TM <= p.M && n0 + G::TNW <= p.N;
+        m0 = __builtin_amdgcn_readfirstlane(tm) * TM, n0 = __builtin_amdgcn_readfirstlane(tn) * TN_;
+        const bool full = m0 + TM <= p.M && n0 + TN_ <= p.N;
         if (!(full && poff_full)) {
             int tid_s = tid;
             asm volatile("" : "+v"(tid_s));  // opaque: the row / chunk terms of the offsets are recomputed when needed instead of living (spilled) across the main loop
-            nt192_piece_offsets<WN>(p.lda, m0, p.M, p.ldb, n0, p.N, tid_s, poff);
+            nt192_piece_offsets(p.lda, m0, p.M, p.ldb, n0, p.N, tid_s, poff);
             poff_full = full;
         }
         Apanel = A + (int64_t)m0 * p.lda;
         Bpanel = B + (int64_t)n0 * p.ldb;
     };
     auto issue_tile = [&](int tile) {  // LDS-DMA of K-tile `tile` into its ring slot
-        const unsigned dst = sbase + slot_of(tile) * G::STAGE;
+        const unsigned dst = sbase + slot_of(tile) * STAGE_BYTES;
 #pragma unroll
-        for (int k = 0; k < G::P; ++k) nt192_stage_piece<WN>(Apanel + tile * TK, Bpanel + tile * TK, poff, dst, k, wave);
+        for (int k = 0; k < P; ++k) nt192_stage_piece(Apanel + tile * TK, Bpanel + tile * TK, poff, dst, k, wave);
     };
     // make tile `nx` visible to every wave (its DMA landed everywhere) and recycle the buffer of tile nx-1, whose
-    // fragments every wave already holds in registers, for tile nx-1+NST.  Its P DMA pieces are issued as one block in
+    // fragments every wave already holds in registers, for tile nx-1+NSTAGE.  Its P DMA pieces are issued as one block in
     // the middle of the following tile body (VT_DMA_ALL), where the partner wave of the SIMD keeps the matrix pipe
     // busy.  With 3 stages one younger tile stays in flight across the barrier.
     auto sync_for = [&](int nx) {
-        if (G::NST == 3 && nx + 1 < nt) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(G::P) : "memory");
+        if (nx + 1 < nt) wait_vmcnt6();
         else wait_vmcnt0();
         raw_barrier();
     };
@@ -288,24 +294,19 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm_nt192_kernel(const NT192Args
     set_tile(blockIdx.x);
     issue_tile(0);
     using GT = GeluTab<EPI>;
-    constexpr bool TABLE = GT::ON && WN == 4;
-    [[maybe_unused]] char* const tab = smem + G::NST * G::STAGE;
-    if constexpr (TABLE) {
+    [[maybe_unused]] char* const tab = smem + NSTAGE * STAGE_BYTES;
+    if constexpr (GT::ON) {
         // visible to every wave long before the first epilogue: the main loop's barriers lie in between
-        for (int e = tid; e < 2 * GT::PER_SIGN; e += G::THREADS) {
+        for (int e = tid; e < 2 * GT::PER_SIGN; e += THREADS) {
             const unsigned sgn = e >= GT::PER_SIGN ? 1u : 0u;
-            const float x = bf2f(bf16_from_bits((sgn << 15) | (unsigned)(e - (int)sgn * GT::PER_SIGN + (GT::LO_EXP << 7))));
-            if constexpr (GT::PAIR) {
-                float gf, df;
-                gelu_erf_and_grad(x, gf, df);
-                ((unsigned*)tab)[e] = bf16_bits(f2bf(gf)) | (bf16_bits(f2bf(df)) << 16);
-            } else {
-                ((bf16_t*)tab)[e] = f2bf(gelu_erf(x));
-            }
+            const bf16_t x = bf16_from_bits((sgn << 15) | (unsigned)(e - (int)sgn * GT::PER_SIGN + (GT::LO_EXP << 7)));
+            bf16_t o, o2;   // what the epilogue writes for x: (x, gelu(x)), or (gelu'(x), gelu(x)) for the pair table
+            epi_value<EPI>(x, x, o, o2);
+            if constexpr (GT::PAIR) ((unsigned*)tab)[e] = bf16_bits(o2) | (bf16_bits(o) << 16);
+            else ((bf16_t*)tab)[e] = o2;
         }
     }
-    constexpr bool PERSIST = WN == 4;   // the 192x96 experiment stays one tile per workgroup
-    for (int it = blockIdx.x; it < nwg; it = PERSIST ? it + (int)gridDim.x : nwg) {
+    for (int it = blockIdx.x; it < nwg; it += (int)gridDim.x) {
     // K-tile 0 of this output tile is already in flight (issued above, or before the previous tile's epilogue)
     // (zeroed by instructions with an inline constant: as plain C++ the compiler keeps a zero register PAIR alive across the whole
     // persistent loop to copy from, and spills it in the instantiations that sit at the register limit)
@@ -322,14 +323,14 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm_nt192_kernel(const NT192Args
         }
     if (it != (int)blockIdx.x) __syncthreads();       // the previous epilogue's LDS image (slots 0-1) has been read back
     if (nt > 1) issue_tile(1);
-    if (G::NST > 2 && nt > 2) issue_tile(2);
-    if (G::NST > 2 && nt > 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * G::P) : "memory");
-    else if (nt > 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(G::P) : "memory");
+    if (nt > 2) issue_tile(2);
+    if (nt > 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * P) : "memory");
+    else if (nt > 1) wait_vmcnt6();
     else wait_vmcnt0();
     raw_barrier();
     bf16x8 xa0[6], xb0[3], xa1[6], xb1[3], ya0[6], yb0[3], ya1[6], yb1[3];
     {   // fragments of tile 0
-        const unsigned s0 = sbase + slot_of(0) * G::STAGE;
+        const unsigned s0 = sbase + slot_of(0) * STAGE_BYTES;
         const unsigned na0 = s0 + a_off0, na1 = na0 ^ 64u, nb0 = s0 + b_off0, nb1 = nb0 ^ 64u;
         VT_DSR(xb0[0], nb0, 0); VT_DSR(xb0[1], nb0, 2048); VT_DSR(xb0[2], nb0, 4096);
         VT_DSR(xa0[0], na0, 0); VT_DSR(xa0[1], na0, 2048); VT_DSR(xa0[2], na0, 4096);
@@ -347,18 +348,18 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm_nt192_kernel(const NT192Args
         {
             const bool more = t + 1 < nt;
             if (more) sync_for(t + 1);
-            const unsigned nb = sbase + slot_of(more ? t + 1 : t) * G::STAGE;
-            const int dma_tile = t + G::NST < nt ? t + G::NST : -1;  // goes into the buffer tile t just vacated
-            const unsigned dma_dst = sbase + slot_of(t) * G::STAGE;
+            const unsigned nb = sbase + slot_of(more ? t + 1 : t) * STAGE_BYTES;
+            const int dma_tile = t + NSTAGE < nt ? t + NSTAGE : -1;  // goes into the buffer tile t just vacated
+            const unsigned dma_dst = sbase + slot_of(t) * STAGE_BYTES;
             VT_STEP(xa0, xb0, xa1, xb1, ya0, yb0, ya1, yb1, nb, true)
             if (++t == nt) break;
         }
         {   // tile t from set Y, prefetch tile t+1 into set X
             const bool more = t + 1 < nt;
             if (more) sync_for(t + 1);
-            const unsigned nb = sbase + slot_of(more ? t + 1 : t) * G::STAGE;
-            const int dma_tile = t + G::NST < nt ? t + G::NST : -1;
-            const unsigned dma_dst = sbase + slot_of(t) * G::STAGE;
+            const unsigned nb = sbase + slot_of(more ? t + 1 : t) * STAGE_BYTES;
+            const int dma_tile = t + NSTAGE < nt ? t + NSTAGE : -1;
+            const unsigned dma_dst = sbase + slot_of(t) * STAGE_BYTES;
             VT_STEP(ya0, yb0, ya1, yb1, xa0, xb0, xa1, xb1, nb, true)
             if (++t == nt) break;
         }
@@ -372,11 +373,9 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm_nt192_kernel(const NT192Args
     // slots 0-1), then write this tile out
     const int em0 = m0, en0 = n0;
     raw_barrier();
-    if constexpr (PERSIST) {
-        if (it + (int)gridDim.x < nwg) {
-            set_tile(it + gridDim.x);
-            issue_tile(0);
-        }
+    if (it + (int)gridDim.x < nwg) {
+        set_tile(it + gridDim.x);
+        issue_tile(0);
     }
 
     if constexpr (EPI != VT_EPI_F32) {
@@ -390,13 +389,11 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm_nt192_kernel(const NT192Args
             const int fr_e = tid_e & 15, fq_e = (tid_e & 63) >> 4;
             // bf16 outputs leave through LDS: after the swapped MFMA a lane owns 4 consecutive columns of 16 different
             // rows, so a direct store instruction touches 16 cache lines with 32 B each (the K -> 0 intercept of
-            // tools/gemm_epilogue_cost.py: 2.4 TB/s of stores).  Staged as bf16(acc + bias) in a [192][TNW] image (row
-            // stride +8 B: the 16 rows of a ds_write_b64 group fall on 16 different bank pairs) and read back row-major,
-            // a store instruction writes 512 contiguous bytes.  GELU / gelu' are applied after the read-back, on the
+            // tools/gemm_epilogue_cost.py: 2.4 TB/s of stores).  Staged as bf16(acc + bias) in a [192][192] image and read
+            // back row-major, a store instruction writes whole lines (nt192_read_back).  GELU / gelu' are applied after the read-back, on the
             // bf16-rounded value (autocast order).
-            constexpr int UPR = G::TNW / 4;             // 8-B units per tile row
-            constexpr int STRIDE = G::TNW * 2 + 8;      // bytes
-            constexpr int RL = G::THREADS / UPR;        // gelu' / aux path: row lanes (10); RL * UPR of the threads are active
+            constexpr int UPR = TN_ / 4;             // 8-B units per tile row
+            constexpr int RL = THREADS / UPR;        // gelu' / aux path: row lanes (10); RL * UPR of the threads are active
             constexpr int NIT = (TM + RL - 1) / RL;
             [[maybe_unused]] bf16x4 uu_pre[NIT];
             if constexpr (MUL) {
@@ -423,7 +420,7 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm_nt192_kernel(const NT192Args
 #pragma unroll
                 for (int j = 0; j < 3; ++j) {
                     const f32x4 v = acc[i][j] + b4[j];
-                    *(bf16x4*)(smem + (wm * 96 + i * 16 + fr_e) * STRIDE + (wn * 12 + j * 4 + fq_e) * 8) = (bf16x4){f2bf(v[0]), f2bf(v[1]), f2bf(v[2]), f2bf(v[3])};
+                    *(bf16x4*)(smem + (wm * 96 + i * 16 + fr_e) * IMG_STRIDE + (wn * 12 + j * 4 + fq_e) * 8) = f2bf4(v);
                 }
             __syncthreads();
             if constexpr (MUL) {
@@ -441,104 +438,30 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm_nt192_kernel(const NT192Args
                         const int row = it * RL + rl;
                         const int m = em0 + row;
                         if (row < TM && m < p.M) {
-                            const bf16x4 h = *(const bf16x4*)(smem + row * STRIDE + c * 8);
-                            const bf16x4 uu = uu_pre[it];
-                            bf16x4 r;
-                            if constexpr (EPI == VT_EPI_BF16_MULAUX) r = mul_aux4(h, uu);
-                            else r = (bf16x4){f2bf(bf2f(h[0]) * gelu_erf_grad(bf2f(uu[0]))), f2bf(bf2f(h[1]) * gelu_erf_grad(bf2f(uu[1]))),
-                                              f2bf(bf2f(h[2]) * gelu_erf_grad(bf2f(uu[2]))), f2bf(bf2f(h[3]) * gelu_erf_grad(bf2f(uu[3])))};
+                            const bf16x4 h = *(const bf16x4*)(smem + row * IMG_STRIDE + c * 8);
+                            bf16x4 r, r2;
+                            epi_values<EPI, 4>(h, uu_pre[it], r, r2);
                             st_stream_any((bf16x4*)((bf16_t*)p.out + (int64_t)m * p.ldo + n), r);
                             cs += (f32x4){bf2f(r[0]), bf2f(r[1]), bf2f(r[2]), bf2f(r[3])};
                         }
                     }
                 }
                 if (p.colsum_partial) {
-                    float* red = (float*)(smem + TM * STRIDE);       // [RL][TNW], behind the staged image
-                    if (rl < RL) *(f32x4*)(red + rl * G::TNW + c * 4) = cs;
+                    float* red = (float*)(smem + TM * IMG_STRIDE);       // [RL][192], behind the staged image
+                    if (rl < RL) *(f32x4*)(red + rl * TN_ + c * 4) = cs;
                     __syncthreads();
-                    if (tid_e < G::TNW && en0 + tid_e < p.N) {
+                    if (tid_e < TN_ && en0 + tid_e < p.N) {
                         float sum = 0.f;
 #pragma unroll
-                        for (int r = 0; r < RL; ++r) sum += red[r * G::TNW + tid_e];
+                        for (int r = 0; r < RL; ++r) sum += red[r * TN_ + tid_e];
                         p.colsum_partial[(int64_t)(em0 / TM) * p.N + en0 + tid_e] = sum;
                     }
                 }
                 continue;
             }
-            // Round 4: 16 bytes per lane on the way out (two 8-byte image reads, ONE global_store_dwordx4: a wave instruction writes 1 KiB).
-            // 8-byte accesses run at 0.54-0.70 of the 16-byte rate (MI355X_MICROARCH, visibility table) and the epilogue is what a round
-            // of this kernel pays outside its main loop (6-13 us, all 256 CUs storing at once).  Needs 8-column alignment of the output.
-            if ((p.N & 7) == 0 && (p.ldo & 7) == 0 && ((EPI != VT_EPI_BF16_GELU && !GG) || (p.ldo2 & 7) == 0)) {
-                constexpr int UPR16 = G::TNW / 8;                        // 16-B units per tile row
-                constexpr int NIT16 = TM * UPR16 / G::THREADS, RB16 = 3;
-                static_assert(NIT16 % RB16 == 0, "read-back batches");
-                // WN = 4: a thread's 9 pieces are 3 row passes of 64 rows x 3 column groups of 64.  Lanes 8r..8r+7 of a wave instruction cover one
-                // 128-byte line of row r (8 full lines per instruction), and every address is one per-thread base plus compile-time terms (the
-                // slot / 24 mapping, kept for the 192x96 experiment, costs ~10 integer instructions per piece).
-                auto piece_row = [&](int u) { if constexpr (WN == 4) return (tid_e >> 3) + (u / 3) * 64; else return (u * G::THREADS + tid_e) / UPR16; };
-                auto piece_col = [&](int u) { if constexpr (WN == 4) return (tid_e & 7) * 8 + (u % 3) * 64; else return ((u * G::THREADS + tid_e) % UPR16) * 8; };
-                auto piece_src = [&](int u) { return (const char*)smem + piece_row(u) * STRIDE + piece_col(u) * 2; };     // 8-byte aligned (row stride 392)
-#pragma unroll 1
-                for (int it0 = 0; it0 < NIT16; it0 += RB16) {
-                    bf16x8 hh[RB16];
-#pragma unroll
-                    for (int u = 0; u < RB16; ++u) {
-                        hh[u] = cat4(*(const bf16x4*)piece_src(it0 + u), *(const bf16x4*)(piece_src(it0 + u) + 8));
-                    }
-#pragma unroll
-                    for (int u = 0; u < RB16; ++u) {
-                        const int m = em0 + piece_row(it0 + u), n = en0 + piece_col(it0 + u);
-                        if (m >= p.M || n >= p.N) continue;
-                        const bf16x8 h = hh[u];
-                        if constexpr (GG) {
-                            bf16x8 g, dg;
-                            gelu_grad_lookup<8, TABLE>(h, tab, g, dg);
-                            st_stream_any((bf16x8*)((bf16_t*)p.out + (int64_t)m * p.ldo + n), dg);
-                            st_stream_any((bf16x8*)((bf16_t*)p.out2 + (int64_t)m * p.ldo2 + n), g);
-                            continue;
-                        }
-                        st_stream_any((bf16x8*)((bf16_t*)p.out + (int64_t)m * p.ldo + n), h);
-                        if constexpr (EPI == VT_EPI_BF16_GELU) {
-                            st_stream_any((bf16x8*)((bf16_t*)p.out2 + (int64_t)m * p.ldo2 + n), gelu_lookup<8, TABLE>(h, (const bf16_t*)tab));
-                        }
-                    }
-                }
-                continue;
-            }
-            // read-back in batches of RB image reads followed by their stores: with one read in flight per store (the compiler's order for
-            // the plain loop) every store waits a full LDS round trip
-            constexpr int NITS = TM * UPR / G::THREADS, RB = 3;
-            static_assert(NITS % RB == 0, "read-back batches");
-#pragma unroll 1
-            for (int it0 = 0; it0 < NITS; it0 += RB) {
-                bf16x4 hh[RB];
-#pragma unroll
-                for (int u = 0; u < RB; ++u) {
-                    const int slot = (it0 + u) * G::THREADS + tid_e;
-                    const int row = slot / UPR, c = slot - row * UPR;
-                    hh[u] = *(const bf16x4*)(smem + row * STRIDE + c * 8);
-                }
-#pragma unroll
-                for (int u = 0; u < RB; ++u) {
-                    const int slot = (it0 + u) * G::THREADS + tid_e;
-                    const int row = slot / UPR, c = slot - row * UPR;
-                    const int m = em0 + row, n = en0 + c * 4;
-                    if (m >= p.M || n >= p.N) continue;
-                    const bf16x4 h = hh[u];
-                    bf16_t* o = (bf16_t*)p.out + (int64_t)m * p.ldo + n;
-                    if constexpr (GG) {
-                        bf16x4 g, dg;
-                        gelu_grad_lookup<4, TABLE>(h, tab, g, dg);
-                        st_stream_any((bf16x4*)o, dg);
-                        st_stream_any((bf16x4*)((bf16_t*)p.out2 + (int64_t)m * p.ldo2 + n), g);
-                        continue;
-                    }
-                    st_stream_any((bf16x4*)o, h);
-                    if constexpr (EPI == VT_EPI_BF16_GELU) {
-                        st_stream_any((bf16x4*)((bf16_t*)p.out2 + (int64_t)m * p.ldo2 + n), gelu_lookup<4, TABLE>(h, (const bf16_t*)tab));
-                    }
-                }
-            }
+            // 16 bytes per lane where every output is 8-column aligned, 8 bytes otherwise
+            if ((p.N & 7) == 0 && (p.ldo & 7) == 0 && ((EPI != VT_EPI_BF16_GELU && !GG) || (p.ldo2 & 7) == 0)) nt192_read_back<EPI, 8>(p, smem, tab, tid_e, em0, en0);
+            else nt192_read_back<EPI, 4>(p, smem, tab, tid_e, em0, en0);
             continue;
         }
     }
@@ -547,7 +470,7 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm_nt192_kernel(const NT192Args
     int tid_x = tid;
     asm volatile("" : "+v"(tid_x));
     const int fr_x = tid_x & 15, fq_x = (tid_x & 63) >> 4;
-    if constexpr (EPI == VT_EPI_F32 && WN == 4) {
+    if constexpr (EPI == VT_EPI_F32) {
         if ((p.N & 3) == 0) {
             // fp32 outputs leave through LDS as well, 96 rows (one wave row) at a time: [96][192] fp32 image, row stride
             // +16 B.  Read back row-major, a wave's load / store instruction covers 768 contiguous bytes of the residual and
@@ -566,7 +489,7 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm_nt192_kernel(const NT192Args
                 // The residual rows of this half are requested FIRST, all NU of them: their latency runs under the staging writes and the
                 // barrier.  (One load per trip of a rolled loop left 8 KiB in flight per CU -- 2 MB on the chip -- and every trip paid a full
                 // memory round trip: the fp32 epilogue cost 11 us more than the bf16 one on the same product.)
-                constexpr int NU = 96 * 48 / G::THREADS;
+                constexpr int NU = 96 * 48 / THREADS;
                 // output row of tile row d without a division per piece: the tile starts at group q0, row r0 of the row map, and with
                 // grp >= 192 it crosses at most one group boundary (other maps take the rolled loop below)
                 const bool cheap_map = omap.grp == 0 || omap.grp >= TM;
@@ -580,7 +503,7 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm_nt192_kernel(const NT192Args
                 constexpr int RBF = 3;             // pieces per batch: one batch of loads is in flight while the previous one is added and stored
                 static_assert(NU % RBF == 0, "residual batches");
                 auto load_res = [&](int u) -> f32x4 {
-                    const int slot = u * G::THREADS + tid_x;
+                    const int slot = u * THREADS + tid_x;
                     const int row = slot / 48, c = slot - row * 48;
                     const int m = em0 + hf * 96 + row, n = en0 + c * 4;
                     return (p.residual && m < p.M && n < p.N) ? *(const f32x4*)(p.residual + orow_of(hf * 96 + row) * p.ldr + n) : (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -611,7 +534,7 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm_nt192_kernel(const NT192Args
                         }
 #pragma unroll
                         for (int uu = 0; uu < RBF; ++uu) {
-                            const int slot = (u0 + uu) * G::THREADS + tid_x;
+                            const int slot = (u0 + uu) * THREADS + tid_x;
                             const int row = slot / 48, c = slot - row * 48;
                             const int m = em0 + hf * 96 + row, n = en0 + c * 4;
                             if (m >= p.M || n >= p.N) continue;
@@ -621,7 +544,7 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm_nt192_kernel(const NT192Args
                             if (p.rowmod) v += *(const f32x4*)(p.rowmod + (int64_t)(m % p.rowmod_period) * p.N + n);
                             if (p.out_scale != 0.f) v *= p.out_scale;
                             *(f32x4*)((float*)p.out + orow * p.ldo + n) = v;
-                            if (p.out2) st_stream((bf16x4*)((bf16_t*)p.out2 + orow * p.ldo2 + n), (bf16x4){f2bf(v[0]), f2bf(v[1]), f2bf(v[2]), f2bf(v[3])});
+                            if (p.out2) st_stream((bf16x4*)((bf16_t*)p.out2 + orow * p.ldo2 + n), f2bf4(v));
                         }
                         if (u0 + RBF < NU) {
 #pragma unroll
@@ -632,7 +555,7 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm_nt192_kernel(const NT192Args
                 }
 #pragma unroll 1
                 for (int u = 0; u < NU; ++u) {
-                    const int slot = u * G::THREADS + tid_x;
+                    const int slot = u * THREADS + tid_x;
                     const int row = slot / 48, c = slot - row * 48;
                     const int m = em0 + hf * 96 + row, n = en0 + c * 4;
                     if (m >= p.M || n >= p.N) continue;
@@ -642,7 +565,7 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm_nt192_kernel(const NT192Args
                     if (p.rowmod) v += *(const f32x4*)(p.rowmod + (int64_t)(m % p.rowmod_period) * p.N + n);
                     if (p.out_scale != 0.f) v *= p.out_scale;
                     *(f32x4*)((float*)p.out + orow * p.ldo + n) = v;
-                    if (p.out2) st_stream((bf16x4*)((bf16_t*)p.out2 + orow * p.ldo2 + n), (bf16x4){f2bf(v[0]), f2bf(v[1]), f2bf(v[2]), f2bf(v[3])});
+                    if (p.out2) st_stream((bf16x4*)((bf16_t*)p.out2 + orow * p.ldo2 + n), f2bf4(v));
                 }
             }
             continue;
@@ -1001,34 +924,27 @@ int vt_gemm_col_block(int forced, int tiles_n, int nwg, int wg_per_cu) {
     return vt_auto_col_block(tiles_n, per_xcd < chunk ? per_xcd : chunk);
 }
 
-// dynamic LDS of gemm_nt192_kernel<EPI, WN>: the ring, and the GELU table behind it
-template <int EPI, int WN>
-static constexpr int nt192_lds_bytes() { return NTGeo<WN>::NST * NTGeo<WN>::STAGE + (WN == 4 ? GeluTab<EPI>::BYTES : 0); }
+// dynamic LDS of gemm_nt192_kernel<EPI>: the ring, and the GELU table behind it
+template <int EPI>
+static constexpr int nt192_lds_bytes() { return NSTAGE * STAGE_BYTES + GeluTab<EPI>::BYTES; }
 
 // Called by vt_gemm_nt / vt_gemm_tn_grouped (vt_gemm.hip) after argument validation.
-template <int WN>
-static int launch_nt192(const vtGemmNT& p, hipStream_t s, int one_tile, int order) {
-    using G = NTGeo<WN>;
+int vt_gemm_nt192_launch(const vtGemmNT& p, hipStream_t s, int one_tile, int order) {
     NT192Args a;
     a.p = p;
     a.tiles_m = (p.M + TM - 1) / TM;
-    a.tiles_n = (p.N + G::TNW - 1) / G::TNW;
+    a.tiles_n = (p.N + TN_ - 1) / TN_;
     const int ntiles = a.tiles_m * a.tiles_n;
-    a.col_block = vt_gemm_col_block(order, a.tiles_n, ntiles, WN == 4 ? 1 : 2);
-    // WN == 4: persistent, one workgroup per CU walks tiles b, b + grid, ...; one_tile (vtGemmNT.tile = 6, the data-parallel backward): one
+    a.col_block = vt_gemm_col_block(order, a.tiles_n, ntiles, 1);
+    // persistent: one workgroup per CU walks tiles b, b + grid, ...; one_tile (vtGemmNT.tile = 6, the data-parallel backward): one
     // tile per workgroup, so that the hardware dispatcher hands tiles to whichever CU is free while a collective's workgroups hold some.
-    const int persist = (WN == 4 && !one_tile) ? vt_gemm_num_cus() : ntiles;
-    const dim3 grid(ntiles < persist ? ntiles : persist), block(G::THREADS);
+    const int persist = one_tile ? ntiles : vt_gemm_num_cus();
+    const dim3 grid(ntiles < persist ? ntiles : persist), block(THREADS);
     return dispatch_epi(p.epi, [&](auto epi) {
-        constexpr int EPI = decltype(epi)::value, LDS = nt192_lds_bytes<EPI, WN>();
-        hipLaunchKernelGGL((gemm_nt192_kernel<EPI, WN>), grid, block, LDS, s, a);
+        constexpr int EPI = decltype(epi)::value, LDS = nt192_lds_bytes<EPI>();
+        hipLaunchKernelGGL((gemm_nt192_kernel<EPI>), grid, block, LDS, s, a);
         return VT_OK;
     });
-}
-
-// half == 0: 192x192 tiles, one workgroup per CU; half != 0: 192x96 tiles, two per CU
-int vt_gemm_nt192_launch(const vtGemmNT& p, hipStream_t s, int half, int one_tile, int order) {
-    return half ? launch_nt192<2>(p, s, one_tile, order) : launch_nt192<4>(p, s, one_tile, order);
 }
 
 int vt_gemm_tn192_launch(const vtGemmTN* ph, int n, hipStream_t s, int burst) {
@@ -1057,8 +973,7 @@ int vt_gemm192_init() {
     for (int epi : VT_EPI_ALL)
         dispatch_epi(epi, [&](auto k) {
             constexpr int EPI = decltype(k)::value;
-            allow((const void*)gemm_nt192_kernel<EPI, 4>, nt192_lds_bytes<EPI, 4>());
-            allow((const void*)gemm_nt192_kernel<EPI, 2>, nt192_lds_bytes<EPI, 2>());
+            allow((const void*)gemm_nt192_kernel<EPI>, nt192_lds_bytes<EPI>());
             return 0;
         });
     allow((const void*)gemm_tn192_kernel, NSTAGE * STAGE_BYTES);
