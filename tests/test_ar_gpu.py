@@ -298,6 +298,43 @@ def test_cached_decode_equals_full_recomputation():
     assert rel(cached, full) < 1e-2, rel(cached, full)
 
 
+def test_invalidate_weight_packs_refreshes_the_gqa_and_swiglu_copies():
+    """A write through `.data` (an EMA swap) bumps no version counter; after vt.invalidate_weight_packs(model) every packed copy follows it,
+    the grouped-query expansion of wqkv and the interleaved w3 / w1 operand of the decode GEMM included: training-branch forward, prefill
+    and one cached decode step equal, bit for bit, those of a second model whose weights were scaled before its first forward."""
+    import video_tokenizer_amd as vt
+
+    def scale(m):
+        for w in (m.layers[0].attention.wqkv.weight, m.layers[0].feed_forward.w1.weight):
+            w.data.copy_(w.data * 1.5)
+
+    def outputs(m, cfg, tok, cond, B):
+        dev = "cuda"
+        m.train()
+        m.cls_embedding.dropout_prob = 0.0
+        with torch.no_grad():
+            train = m(tok[:, :-1].to(dev), cond.to(dev))[0].clone()
+            m.eval()
+            m.setup_caches(B, cfg["max_seq_len"] + 1)
+            with m.sampling():
+                prefill = m(None, cond.to(dev), torch.arange(0, 1, device=dev))[0].clone()
+                step = m(tok[:, :1].to(dev), None, torch.tensor([1], device=dev, dtype=torch.int))[0].clone()
+            m.reset_caches()
+        return train, prefill, step
+
+    m, cfg, sd, (tok, cond), B = build("class_S2_gqa")
+    before = outputs(m, cfg, tok, cond, B)
+    scale(m)
+    vt.invalidate_weight_packs(m)
+    after = outputs(m, cfg, tok, cond, B)
+    m2 = build("class_S2_gqa")[0]
+    scale(m2)
+    want = outputs(m2, cfg, tok, cond, B)
+    for name, a, w, b in zip(("training forward", "prefill", "decode step"), after, want, before):
+        assert torch.equal(a, w), name
+        assert not torch.equal(a, b), name
+
+
 def test_frame_prediction_prefill_equals_full_forward():
     m, cfg, sd, (tok, cond), B = build("frame_S2")
     m.eval()

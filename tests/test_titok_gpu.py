@@ -10,6 +10,7 @@ import torch.nn.functional as F
 from oracle import inputs as gen
 from oracle import titok_oracle as T
 from oracle.larp_oracle import _rb
+from tests import gated_layer_reference as GR
 
 pytestmark = pytest.mark.gpu
 
@@ -135,7 +136,7 @@ def test_one_gated_layer_matches_oracle(vt):
     cos, sin = vt.titok.rope_tables(32, cfg["grid"])
     dev = [sd[k].clone().cuda().requires_grad_(True) for k in names]
     xd = x.clone().cuda().requires_grad_(True)
-    out = vt.titok.GatedLayer.apply(xd, cos.cuda(), sin.cuda(), H, scale, None, *dev)
+    out = GR.GatedLayer.apply(xd, cos.cuda(), sin.cuda(), H, scale, *dev)
     (out * up.cuda()).sum().backward()
     assert rel(out, ref) < 5e-3
     assert rel(xd.grad, xr.grad) < 2e-2
@@ -301,12 +302,12 @@ def test_first_token_registry_names_resolve_and_run_at_the_reference_geometry(vt
         assert g is not None and bool(torch.isfinite(g).all()) and float(g.abs().sum()) > 0
 
 
-def test_packed_weights_follow_the_module_not_the_address(vt, monkeypatch):
+def test_packed_weights_follow_the_module_not_the_address(vt):
     """Round-2 advisor finding: the pooled GatedStack workspaces are keyed by geometry and held packed bf16 weights identified
     only by (parameter address, _version).  A second model of the same geometry built after the first was deleted gets the same
     addresses from the caching allocator and the same version counters -- and used to run on the FIRST model's matrices.  The key
-    now carries the owning module's identity: model B must equal its own per-layer composition (VT_GATED_PYTHON=1) bit for
-    bit.  `p.data.copy_` does not bump `_version`: after vt.invalidate_weight_packs(model) the copies are re-made."""
+    now carries the owning module's identity: model B must equal its own per-layer composition (gated_layer_reference, which packs
+    on every call) bit for bit.  `p.data.copy_` does not bump `_version`: after vt.invalidate_weight_packs(model) the copies are re-made."""
     cos, sin = vt.titok.rope_tables(32, [2, 4, 4])
     fr = (cos.cuda(), sin.cuda())
     x = torch.from_numpy(gen.normal((2, 64, 256), 911, 0.5)).cuda()
@@ -319,7 +320,6 @@ def test_packed_weights_follow_the_module_not_the_address(vt, monkeypatch):
                 torch.nn.init.normal_(p_, 0.0, 0.05)
         return blk
 
-    monkeypatch.setenv("VT_GATED_PYTHON", "0")
     a = fresh(1)
     with torch.no_grad():
         out_a = a(x, fr).clone()
@@ -330,23 +330,20 @@ def test_packed_weights_follow_the_module_not_the_address(vt, monkeypatch):
     same_addresses = [p_.data_ptr() for p_ in b.parameters()] == ptrs_a     # the situation the finding describes (usual, not guaranteed)
     with torch.no_grad():
         out_b = b(x, fr).clone()
-        monkeypatch.setenv("VT_GATED_PYTHON", "1")
-        ref_b = b(x, fr).clone()
-        monkeypatch.setenv("VT_GATED_PYTHON", "0")
+        ref_b = GR.reference_stack(b, x, fr).clone()
     assert torch.equal(out_b, ref_b), f"model B ran on stale packed weights (same addresses: {same_addresses})"
     assert not torch.equal(out_b, out_a)
     with torch.no_grad():
         b.attn_layer[0].to_qkv.weight.data.copy_(b.attn_layer[0].to_qkv.weight.data * 1.5)    # no _version bump
         vt.invalidate_weight_packs(b)
         out_c = b(x, fr).clone()
-        monkeypatch.setenv("VT_GATED_PYTHON", "1")
-        ref_c = b(x, fr).clone()
+        ref_c = GR.reference_stack(b, x, fr).clone()
     assert torch.equal(out_c, ref_c) and not torch.equal(out_c, out_b)
 
 
-def test_gated_stack_engine_equals_python_composition(vt, monkeypatch):
+def test_gated_stack_engine_equals_python_composition(vt):
     """vt_gated_stack_forward / _backward (one C++ enqueue per direction) == the per-layer Python composition of the same
-    kernels (titok.GatedLayer), bit for bit: output, input gradient and every parameter gradient of a 4-layer stack, incl.
+    kernels (gated_layer_reference.GatedLayer), bit for bit: output, input gradient and every parameter gradient of a 4-layer stack, incl.
     the fused 1/sqrt(i+1) rescale (vtGemmNT.out_scale) and the 64-padded GEGLU width (inner 704 -> 704, 1376 -> 1408)."""
     for width, heads in ((256, 4), (512, 8)):
         torch.manual_seed(0)
@@ -354,15 +351,15 @@ def test_gated_stack_engine_equals_python_composition(vt, monkeypatch):
         for p_ in blk.parameters():
             torch.nn.init.normal_(p_, 0.0, 0.05) if p_.dim() > 1 else torch.nn.init.normal_(p_, 1.0 if "norm" in "" else 0.5, 0.1)
         cos, sin = vt.titok.rope_tables(32, [2, 4, 4])
+        fr = (cos.cuda(), sin.cuda())
         x = torch.from_numpy(gen.normal((2, 64, width), 901, 0.5)).cuda()
         up = torch.from_numpy(gen.normal((2, 64, width), 902)).cuda()
         res = {}
-        for mode in ("1", "0"):
-            monkeypatch.setenv("VT_GATED_PYTHON", mode)
+        for mode, run in (("1", lambda xi: GR.reference_stack(blk, xi, fr)), ("0", lambda xi: blk(xi, fr))):
             for p_ in blk.parameters():
                 p_.grad = None
             xi = x.clone().requires_grad_(True)
-            out = blk(xi, (cos.cuda(), sin.cuda()))
+            out = run(xi)
             (out * up).sum().backward()
             torch.cuda.synchronize()
             res[mode] = (out.detach().clone(), xi.grad.clone(), {n: p_.grad.clone() for n, p_ in blk.named_parameters()})
@@ -370,11 +367,10 @@ def test_gated_stack_engine_equals_python_composition(vt, monkeypatch):
         for n in res["0"][2]:
             assert torch.equal(res["0"][2][n], res["1"][2][n]), n
         # a second forward/backward through the pooled workspace (weights unchanged: no re-pack) gives the same bits
-        monkeypatch.setenv("VT_GATED_PYTHON", "0")
         xi = x.clone().requires_grad_(True)
-        out = blk(xi, (cos.cuda(), sin.cuda()))
+        out = blk(xi, fr)
         assert torch.equal(out, res["0"][0])
         with torch.no_grad():                       # and after a weight update the packed copies follow
             blk.attn_layer[0].to_qkv.weight.mul_(1.01)
-        out2 = blk(x, (cos.cuda(), sin.cuda()))
-        assert not torch.equal(out2, res["0"][0])
+        out2 = blk(x, fr)
+        assert not torch.equal(out2, res["0"][0]) and torch.equal(out2, GR.reference_stack(blk, x, fr))

@@ -29,6 +29,7 @@ def graph_replay_safe():
 
 
 from . import hip  # noqa: F401  (ctypes binding; loading is lazy)
+from . import packs  # noqa: F401
 from . import config  # noqa: F401
 from .registry import make, models, register  # noqa: F401
 from . import transformer, bottleneck, larp_tokenizer, loss, titok, stat, sq, larp_ar  # noqa: F401  (registers the classes)
@@ -42,13 +43,11 @@ from .design import (AutoEncoder, CrossAttention, Encoder, FirstFrameEncoder, Le
 
 
 def invalidate_weight_packs(module):
-    """Drop every cached bf16 operand copy below `module`.  The copies are keyed by (owner identity, parameter address,
-    `_version`); optimizer steps, load_state_dict and .to() change one of these, a write through `.data` (`p.data.copy_(...)`,
-    e.g. a hand-rolled EMA swap) does not -- call this after such a write."""
+    """Drop every cached bf16 operand copy below `module` (packs.py).  The copies are keyed by (owner, parameter address, `_version`);
+    optimizer steps, load_state_dict and .to() change one of these, a write through `.data` (`p.data.copy_(...)`, e.g. a hand-rolled
+    EMA swap) does not -- call this after such a write."""
+    packs.invalidate(module)
     for m in module.modules():
-        if hasattr(m, "invalidate_packs"):
-            m.invalidate_packs()
-        m.__dict__.pop("_vt_pack", None)                      # larp_ar._pack caches
         eng = m.__dict__.get("_engine")
         if eng is not None:
             eng.param_epoch = getattr(eng, "param_epoch", 0) + 1   # the tokenizer engine re-packs on the next forward

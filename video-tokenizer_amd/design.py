@@ -16,7 +16,7 @@ import torch.nn as nn
 from torch.nn import functional as TF
 
 from . import functional as F_
-from . import hip
+from . import hip, packs
 from .fsq import FSQ
 from .registry import register
 from .titok import get_model_dims, rope_tables
@@ -36,21 +36,6 @@ class RMSNorm(nn.Module):
 
     def forward(self, x):
         raise hip.HipError("design.RMSNorm has no stand-alone forward: the layer that owns it (design.CrossAttention) applies it in its fused pass")
-
-
-def _pack(owner, names, k_pad=None):
-    """bf16 [N, K] and [K, N] operand copies of one weight of `owner` (dotted names allowed), or of several concatenated along N; re-made when
-    a weight changes"""
-    ws = [owner.get_parameter(n + ".weight") for n in names]
-    key = tuple((w.data_ptr(), w._version) for w in ws)
-    cache = owner.__dict__.setdefault("_vt_pack", {})
-    hit = cache.get(names)
-    if hit is None or hit[0] != key:
-        with torch.no_grad():
-            w = torch.cat([t.detach() for t in ws], dim=0) if len(ws) > 1 else ws[0].detach()
-            hit = (key, hip.pack_weight(w.float().contiguous(), k_pad=k_pad))
-        cache[names] = hit
-    return hit[1]
 
 
 class CrossAttention(nn.Module):
@@ -75,14 +60,12 @@ class CrossAttention(nn.Module):
         self.k_norm = RMSNorm(self.head_dim)
         self.out_proj = nn.Linear(dim, dim, bias=False)
 
-    def _pack(self, *names):
-        return _pack(self, names)
-
     def forward(self, x, context):
         hip.require_gpu(x, context, *self.parameters())
         return F_.CrossAttentionLayer.apply(x, context, self.norm_q.weight, self.norm_kv.weight, self.to_q.weight, self.to_kv.weight,
                                             self.to_gate.weight, self.q_norm.weight, self.k_norm.weight, self.out_proj.weight, self.heads,
-                                            self.norm_q.eps, self._pack("to_q", "to_gate"), self._pack("to_kv"), self._pack("out_proj"))
+                                            self.norm_q.eps, packs.get(self, ("to_q", "to_gate")), packs.get(self, ("to_kv",)),
+                                            packs.get(self, ("out_proj",)))
 
 
 class SelfAttention(nn.Module):
@@ -106,8 +89,8 @@ class SelfAttention(nn.Module):
     def forward(self, x, cos, sin, res_scale):
         hip.require_gpu(x, cos, sin, res_scale, *self.parameters())
         return F_.SelfAttentionLayer.apply(x, cos, sin, res_scale, self.norm.weight, self.to_qkv.weight, self.to_gate.weight, self.q_norm.weight,
-                                           self.k_norm.weight, self.out_proj.weight, self.heads, self.norm.eps, _pack(self, ("to_qkv", "to_gate")),
-                                           _pack(self, ("out_proj",)))
+                                           self.k_norm.weight, self.out_proj.weight, self.heads, self.norm.eps, packs.get(self, ("to_qkv", "to_gate")),
+                                           packs.get(self, ("out_proj",)))
 
 
 class GEGLU(nn.Module):
@@ -154,8 +137,8 @@ class TransformerBlock(nn.Module):
             x = F_.ResidualScale.apply(x, self.cross_attn(x, context), self.res_scale_ca)
         ffn = self.ffn
         inner = ffn[3].weight.shape[1]
-        return F_.FeedForwardLayer.apply(x, self.res_scale_ffn, ffn[0].weight, ffn[1].weight, ffn[3].weight, ffn[0].eps, _pack(self, ("ffn.1",)),
-                                         _pack(self, ("ffn.3",), k_pad=F_._pad64(inner)))
+        return F_.FeedForwardLayer.apply(x, self.res_scale_ffn, ffn[0].weight, ffn[1].weight, ffn[3].weight, ffn[0].eps, packs.get(self, ("ffn.1",)),
+                                         packs.get(self, ("ffn.3",), k_pad=F_._pad64(inner)))
 
 
 class TransformerStack(nn.Module):

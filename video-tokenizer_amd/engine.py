@@ -13,6 +13,7 @@ import os
 import torch
 
 from . import hip
+from .functional import BLOCK_PARAM_NAMES, block_params
 
 
 def _flat_order(model):
@@ -22,17 +23,12 @@ def _flat_order(model):
     de, dd = model.encoder.depth, model.decoder.depth
     out = []
 
-    def blk(side, i, stage, with_fc2_b_of=None):
-        b = getattr(model, side).blocks[i]
-        pre = f"{side}.blocks.{i}."
-        for n, p in (("norm1.weight", b.norm1.weight), ("norm1.bias", b.norm1.bias), ("attn.qkv.weight", b.attn.qkv.weight),
-                     ("attn.proj.weight", b.attn.proj.weight), ("attn.proj.bias", b.attn.proj.bias), ("norm2.weight", b.norm2.weight),
-                     ("norm2.bias", b.norm2.bias), ("mlp.fc1.weight", b.mlp.fc1.weight), ("mlp.fc1.bias", b.mlp.fc1.bias),
-                     ("mlp.fc2.weight", b.mlp.fc2.weight)):
-            out.append((pre + n, p, stage))
+    def blk(side, i, stage):          # all of the block but fc2.bias, whose gradient the stage before has already written
+        ps = block_params([getattr(model, side).blocks[i]])
+        out.extend((f"{side}.blocks.{i}.{n}", p, stage) for n, p in zip(BLOCK_PARAM_NAMES[:-1], ps))
 
     def fc2b(side, i, stage):
-        out.append((f"{side}.blocks.{i}.mlp.fc2.bias", getattr(model, side).blocks[i].mlp.fc2.bias, stage))
+        out.append((f"{side}.blocks.{i}.{BLOCK_PARAM_NAMES[-1]}", block_params([getattr(model, side).blocks[i]])[-1], stage))
 
     fl = model.final_layer
     out += [("final_layer.linear.weight", fl.linear.weight, 0), ("final_layer.linear.bias", fl.linear.bias, 0),
@@ -68,12 +64,9 @@ class _Tensors:
         de, dd = model.encoder.depth, model.decoder.depth
         self.enc = (hip.BlockTensors * de)()
         self.dec = (hip.BlockTensors * dd)()
-        names = {"norm1_w": "norm1.weight", "norm1_b": "norm1.bias", "qkv_w": "attn.qkv.weight", "proj_w": "attn.proj.weight",
-                 "proj_b": "attn.proj.bias", "norm2_w": "norm2.weight", "norm2_b": "norm2.bias", "fc1_w": "mlp.fc1.weight",
-                 "fc1_b": "mlp.fc1.bias", "fc2_w": "mlp.fc2.weight", "fc2_b": "mlp.fc2.bias"}
         for side, arr, depth in (("encoder", self.enc, de), ("decoder", self.dec, dd)):
             for i in range(depth):
-                for f, n in names.items():
+                for f, n in zip(hip.BLOCK_FIELDS, BLOCK_PARAM_NAMES):
                     setattr(arr[i], f, get(f"{side}.blocks.{i}.{n}"))
         t = hip.TokenizerTensors()
         t.pe_w, t.pe_b = get("x_embedder.proj.weight"), get("x_embedder.proj.bias")

@@ -16,6 +16,8 @@ The layers of the reference's `autoencoder_design` are here as well: CrossAttent
 fp32 final norm); design.py holds their parameters.
 """
 import ctypes
+import functools
+import operator
 
 import torch
 
@@ -30,48 +32,90 @@ def _zeros(rows, cols, dev, dtype=torch.bfloat16):
     return torch.zeros(rows, cols, device=dev, dtype=dtype)
 
 
-PARAMS_PER_BLOCK = 11
-BLOCK_PARAM_NAMES = ("norm1.weight", "norm1.bias", "attn.qkv.weight", "attn.proj.weight", "attn.proj.bias",
-                     "norm2.weight", "norm2.bias", "mlp.fc1.weight", "mlp.fc1.bias", "mlp.fc2.weight", "mlp.fc2.bias")
+# The parameters of one block / one gated layer, in the field order of the C structs: the only spelling of either list.
+BLOCK_PARAM_NAMES = ("norm1.weight", "norm1.bias", "attn.qkv.weight", "attn.proj.weight", "attn.proj.bias",          # hip.BLOCK_FIELDS; below a
+                     "norm2.weight", "norm2.bias", "mlp.fc1.weight", "mlp.fc1.bias", "mlp.fc2.weight", "mlp.fc2.bias")  # transformer.Block / SimpleBlock
+GATED_PARAM_NAMES = ("attn_layer.{0}.to_qkv.weight", "attn_layer.{0}.q_norm.weight", "attn_layer.{0}.q_norm.bias",    # hip.GATED_FIELDS; below a
+                     "attn_layer.{0}.k_norm.weight", "attn_layer.{0}.k_norm.bias", "attn_layer.{0}.out_proj.weight",  # titok.ResidualAttentionBlock,
+                     "ffd_layer.{0}.0.weight", "ffd_layer.{0}.0.bias", "ffd_layer.{0}.1.weight", "ffd_layer.{0}.3.weight")   # {0} = the layer
+PARAMS_PER_BLOCK, PARAMS_PER_GATED_LAYER = len(hip.BLOCK_FIELDS), len(hip.GATED_FIELDS)
+assert len(BLOCK_PARAM_NAMES) == PARAMS_PER_BLOCK and len(GATED_PARAM_NAMES) == PARAMS_PER_GATED_LAYER
+_block_getter = operator.attrgetter(*BLOCK_PARAM_NAMES)
 
 
 def block_params(blocks):
     """flat parameter list of an nn.ModuleList / nn.Sequential of transformer.Block in BLOCK_PARAM_NAMES order"""
-    out = []
-    for b in blocks:
-        out += [b.norm1.weight, b.norm1.bias, b.attn.qkv.weight, b.attn.proj.weight, b.attn.proj.bias,
-                b.norm2.weight, b.norm2.bias, b.mlp.fc1.weight, b.mlp.fc1.bias, b.mlp.fc2.weight, b.mlp.fc2.bias]
-    return out
+    return [p for b in blocks for p in _block_getter(b)]
 
 
-_STACKS = {}       # (B, L, D, H, depth) -> (handle, workspace bytes)
-_WS_POOL = {}      # same key -> zero-initialised workspaces whose backward is done (their padded rows are still zero)
+@functools.lru_cache(maxsize=None)
+def _gated_getter(i):
+    return operator.attrgetter(*(n.format(i) for n in GATED_PARAM_NAMES))
 
 
-def _stack(key):
-    h = _STACKS.get(key)
-    if h is None:
-        cfg = hip.StackConfig(*key)
-        out = ctypes.c_void_p()
-        hip.check(hip.lib().vt_stack_create(ctypes.byref(cfg), ctypes.byref(out)), "vt_stack_create")
-        h = (out, int(hip.lib().vt_stack_workspace_bytes(out)))
-        _STACKS[key] = h
-    return h
+def gated_params(stack):
+    """flat parameter list of a titok.ResidualAttentionBlock in GATED_PARAM_NAMES order, layer by layer"""
+    return [p for i in range(stack.num_layer) for p in _gated_getter(i)(stack)]
 
 
-def _take_ws(key, nbytes, dev):
-    pool = _WS_POOL.setdefault((key, str(dev)), [])
-    if pool:
-        return pool.pop()
-    return torch.zeros(nbytes, dtype=torch.uint8, device=dev)   # = vt_stack_init_workspace
+class _Workspace:
+    """a pooled workspace: its bytes, and the pack key (packs.pack_key) of the weight copies a gated stack left in them"""
+    __slots__ = ("buf", "pack_key")
+
+    def __init__(self, buf):
+        self.buf, self.pack_key = buf, None
 
 
-def _block_array(tensors, depth):
-    arr = (hip.BlockTensors * depth)()
-    for i in range(depth):
-        for j, name in enumerate(hip.BLOCK_FIELDS):
-            setattr(arr[i], name, tensors[i * PARAMS_PER_BLOCK + j].data_ptr())
-    return arr
+class _StackPool:
+    """Host side of one stack engine (`prefix`_create / _workspace_bytes, its config and per-layer tensor structs): one handle per geometry,
+    the ctypes arrays of a call, and the workspaces.  A workspace is zero-initialised (= `prefix`_init_workspace), stays with a forward until its
+    backward has run, and is pooled again after that (or right behind an inference forward: stream order); its padded rows are still zero then."""
+
+    def __init__(self, prefix, config, tensors, fields):
+        self.prefix, self.config, self.tensors, self.fields = prefix, config, tensors, fields
+        self.handles = {}      # geometry -> (handle, workspace bytes)
+        self.free = {}         # (geometry, device) -> [_Workspace]
+
+    def handle(self, key):
+        h = self.handles.get(key)
+        if h is None:
+            cfg = self.config(*key)
+            out = ctypes.c_void_p()
+            hip.check(getattr(hip.lib(), self.prefix + "_create")(ctypes.byref(cfg), ctypes.byref(out)), self.prefix + "_create")
+            h = self.handles[key] = (out, int(getattr(hip.lib(), self.prefix + "_workspace_bytes")(out)))
+        return h
+
+    def array(self, tensors, depth):
+        arr = (self.tensors * depth)()
+        for i in range(depth):
+            for j, name in enumerate(self.fields):
+                setattr(arr[i], name, tensors[i * len(self.fields) + j].data_ptr())
+        return arr
+
+    def take(self, key, dev):
+        free = self.free.setdefault((key, str(dev)), [])
+        return free.pop() if free else _Workspace(torch.zeros(self.handle(key)[1], dtype=torch.uint8, device=dev))
+
+    def recycle(self, key, ws):
+        self.free[(key, str(ws.buf.device))].append(ws)
+
+    def after_forward(self, ctx, key, ws, params, tabs):
+        if any(ctx.needs_input_grad):     # a backward may follow: the activations stay in ws until then
+            ctx.key, ctx.ws, ctx.params, ctx.tabs = key, ws, params, tabs
+        else:                             # inference: the workspace is free again behind this forward
+            self.recycle(key, ws)
+
+    def claim(self, ctx, who):
+        """the workspace of ctx's forward, once: the caller recycles it behind its backward launch"""
+        ws, ctx.ws = ctx.ws, None
+        if ws is None:
+            raise RuntimeError(f"{who}: second backward through the same forward (its workspace was recycled)")
+        return ws
+
+
+_BLOCKS = _StackPool("vt_stack", hip.StackConfig, hip.BlockTensors, hip.BLOCK_FIELDS)                 # geometry (B, L, D, H, depth)
+_GATED = _StackPool("vt_gated_stack", hip.GatedStackConfig, hip.GatedLayerTensors, hip.GATED_FIELDS)  # geometry (B, L, D, H, depth, inner)
+_stack, _block_array = _BLOCKS.handle, _BLOCKS.array      # for callers that drive the C entry points themselves (tests/test_simple_gpu.py)
 
 
 class BlockStack(torch.autograd.Function):
@@ -97,35 +141,29 @@ class BlockStack(torch.autograd.Function):
             assert cos.dtype == torch.float32 and sin.dtype == torch.float32 and cos.shape == (L, 32) == sin.shape
             cos, sin = cos.contiguous(), sin.contiguous()
         key = (B, L, D, n_head, depth)
-        handle, nbytes = _stack(key)
+        handle, _ = _BLOCKS.handle(key)
         params = tuple(p_.detach().float().contiguous() for p_ in params)
-        ws = _take_ws(key, nbytes, x.device)
+        ws = _BLOCKS.take(key, x.device)
         xin = x.contiguous()
         out = torch.empty_like(xin)
-        hip.check(hip.lib().vt_stack_forward_rotary(handle, _block_array(params, depth), hip.ptr(cos), hip.ptr(sin), hip.ptr(xin), hip.ptr(ws),
+        hip.check(hip.lib().vt_stack_forward_rotary(handle, _BLOCKS.array(params, depth), hip.ptr(cos), hip.ptr(sin), hip.ptr(xin), hip.ptr(ws.buf),
                                                     hip.ptr(out), hip.stream()), "vt_stack_forward_rotary")
-        if any(ctx.needs_input_grad):     # a backward may follow: the activations stay in ws until then
-            ctx.key, ctx.ws, ctx.params, ctx.tabs, ctx.done = key, ws, params, (cos, sin), False
-        else:                             # inference: the workspace is free again behind this forward (stream order)
-            _WS_POOL[(key, str(x.device))].append(ws)
+        _BLOCKS.after_forward(ctx, key, ws, params, (cos, sin))
         return out
 
     @staticmethod
     def backward(ctx, dy):
-        if ctx.done:
-            raise RuntimeError("BlockStack: second backward through the same forward (its workspace was recycled)")
+        ws = _BLOCKS.claim(ctx, "BlockStack")
         B, L, D, H, depth = ctx.key
-        handle, _ = _stack(ctx.key)
+        handle, _ = _BLOCKS.handle(ctx.key)
         need = ctx.needs_input_grad[4:]
         grads = [torch.empty_like(p_) for p_ in ctx.params]     # LayerNorm / bias gradients are always produced
         dx = torch.empty(B, L, D, device=dy.device, dtype=torch.float32)
         dyc = dy.contiguous().float()
         cos, sin = ctx.tabs
-        hip.check(hip.lib().vt_stack_backward_rotary(handle, _block_array(ctx.params, depth), hip.ptr(cos), hip.ptr(sin), hip.ptr(dyc), hip.ptr(ctx.ws),
-                                                     _block_array(grads, depth), hip.ptr(dx), int(any(need)), hip.stream()), "vt_stack_backward_rotary")
-        ctx.done = True
-        _WS_POOL[(ctx.key, str(dy.device))].append(ctx.ws)
-        ctx.ws = None
+        hip.check(hip.lib().vt_stack_backward_rotary(handle, _BLOCKS.array(ctx.params, depth), hip.ptr(cos), hip.ptr(sin), hip.ptr(dyc), hip.ptr(ws.buf),
+                                                     _BLOCKS.array(grads, depth), hip.ptr(dx), int(any(need)), hip.stream()), "vt_stack_backward_rotary")
+        _BLOCKS.recycle(ctx.key, ws)
         return (dx, None, None, None, *[g if n else None for g, n in zip(grads, need)])
 
 
@@ -137,37 +175,11 @@ def rotary_block_stack(x, blocks, n_head, cos, sin):
     return BlockStack.apply(x, cos, sin, n_head, *block_params(blocks))
 
 
-# ------------------------------------------------------------------------------------------------------------------------
-# stack of the TiTok-style gated layers (models/model_new/base/transformer.py:66-91) as one engine call per direction
-# ------------------------------------------------------------------------------------------------------------------------
-PARAMS_PER_GATED_LAYER = 10   # hip.GATED_FIELDS order: to_qkv, q_norm w/b, k_norm w/b, out_proj, ffd LayerNorm w/b, ffd.1, ffd.3
-_GSTACKS = {}
-
-
-def _gstack(key):
-    h = _GSTACKS.get(key)
-    if h is None:
-        cfg = hip.GatedStackConfig(*key)
-        out = ctypes.c_void_p()
-        hip.check(hip.lib().vt_gated_stack_create(ctypes.byref(cfg), ctypes.byref(out)), "vt_gated_stack_create")
-        h = (out, int(hip.lib().vt_gated_stack_workspace_bytes(out)))
-        _GSTACKS[key] = h
-    return h
-
-
-def _gated_array(tensors, depth):
-    arr = (hip.GatedLayerTensors * depth)()
-    for i in range(depth):
-        for j, name in enumerate(hip.GATED_FIELDS):
-            setattr(arr[i], name, tensors[i * PARAMS_PER_GATED_LAYER + j].data_ptr())
-    return arr
-
-
 class GatedStack(torch.autograd.Function):
-    """depth x {x += Attn(x); x += ffd(x); x /= sqrt(i+1)} on x fp32 [B, L, D] (B * L % 64 == 0, D = 64 * heads): ONE
-    vt_gated_stack_forward / _backward call each (11 launches per layer forward, 17 backward, issued by the C++ engine).  The
-    workspace carries the saved activations and the bf16 operand copies of the weights; `pack_key` identifies the weight
-    versions a workspace was packed for."""
+    """The stack of TiTok-style gated layers (models/model_new/base/transformer.py:66-91): depth x {x += Attn(x); x += ffd(x); x /= sqrt(i+1)}
+    on x fp32 [B, L, D] (B * L % 64 == 0, D = 64 * heads): ONE vt_gated_stack_forward / _backward call each (11 launches per layer forward,
+    17 backward, issued by the C++ engine).  params: GATED_PARAM_NAMES order per layer.  The workspace carries the saved activations and the
+    bf16 operand copies of the weights; `pack_key` (packs.pack_key) identifies the weight versions a workspace was packed for."""
 
     @staticmethod
     def forward(ctx, x, cos, sin, n_head, pack_key, *params):
@@ -178,36 +190,30 @@ class GatedStack(torch.autograd.Function):
         assert depth * PARAMS_PER_GATED_LAYER == len(params)
         inner = params[9].shape[1]
         key = (B, L, D, n_head, depth, inner)
-        handle, nbytes = _gstack(key)
+        handle, _ = _GATED.handle(key)
         params = tuple(p_.detach().float().contiguous() for p_ in params)
-        ws = _take_ws(("gated",) + key, nbytes, x.device)
-        repack = getattr(ws, "_vt_pack_key", None) != pack_key
-        ws._vt_pack_key = pack_key
+        ws = _GATED.take(key, x.device)
+        repack = ws.pack_key != pack_key
+        ws.pack_key = pack_key
         xin = x.contiguous().float()
         out = torch.empty_like(xin)
-        hip.check(hip.lib().vt_gated_stack_forward(handle, _gated_array(params, depth), hip.ptr(cos), hip.ptr(sin), hip.ptr(xin), hip.ptr(ws), hip.ptr(out),
-                                                   int(repack), hip.stream()), "vt_gated_stack_forward")
-        if any(ctx.needs_input_grad):
-            ctx.key, ctx.ws, ctx.params, ctx.tabs, ctx.done = key, ws, params, (cos, sin), False
-        else:
-            _WS_POOL[(("gated",) + key, str(x.device))].append(ws)
+        hip.check(hip.lib().vt_gated_stack_forward(handle, _GATED.array(params, depth), hip.ptr(cos), hip.ptr(sin), hip.ptr(xin), hip.ptr(ws.buf),
+                                                   hip.ptr(out), int(repack), hip.stream()), "vt_gated_stack_forward")
+        _GATED.after_forward(ctx, key, ws, params, (cos, sin))
         return out
 
     @staticmethod
     def backward(ctx, dy):
-        if ctx.done:
-            raise RuntimeError("GatedStack: second backward through the same forward (its workspace was recycled)")
+        ws = _GATED.claim(ctx, "GatedStack")
         B, L, D, H, depth, inner = ctx.key
-        handle, _ = _gstack(ctx.key)
+        handle, _ = _GATED.handle(ctx.key)
         grads = [torch.empty_like(p_) for p_ in ctx.params]
         dx = torch.empty(B, L, D, device=dy.device, dtype=torch.float32)
         dyc = dy.contiguous().float()
         cos, sin = ctx.tabs
-        hip.check(hip.lib().vt_gated_stack_backward(handle, _gated_array(ctx.params, depth), hip.ptr(cos), hip.ptr(sin), hip.ptr(dyc), hip.ptr(ctx.ws),
-                                                    _gated_array(grads, depth), hip.ptr(dx), hip.stream()), "vt_gated_stack_backward")
-        ctx.done = True
-        _WS_POOL[(("gated",) + ctx.key, str(dy.device))].append(ctx.ws)
-        ctx.ws = None
+        hip.check(hip.lib().vt_gated_stack_backward(handle, _GATED.array(ctx.params, depth), hip.ptr(cos), hip.ptr(sin), hip.ptr(dyc), hip.ptr(ws.buf),
+                                                    _GATED.array(grads, depth), hip.ptr(dx), hip.stream()), "vt_gated_stack_backward")
+        _GATED.recycle(ctx.key, ws)
         need = ctx.needs_input_grad[5:]
         return (dx, None, None, None, None, *[g if n else None for g, n in zip(grads, need)])
 

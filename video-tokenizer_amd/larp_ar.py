@@ -24,10 +24,10 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import hip
+from . import hip, packs
 from .embed import get_1d_sincos_pos_embed_from_grid
 from .functional import Linear as LinearFn
-from .functional import RMSNormRows
+from .functional import RMSNormRows, _rows64
 from .pretrained import LocalPretrainedMixin
 from .registry import models as _registry
 
@@ -65,17 +65,8 @@ class ModelArgs:
 
 # ------------------------------------------------------------------------------------------------ autograd functions over the kernels
 def _pack(mod, *names):
-    """bf16 [N, K] and [K, N] operand copies of one weight, or of several concatenated along N; re-made when a weight changes"""
-    ws = [getattr(mod, n).weight for n in names]
-    key = tuple((w.data_ptr(), w._version) for w in ws)
-    cache = mod.__dict__.setdefault("_vt_pack", {})
-    hit = cache.get(names)
-    if hit is None or hit[0] != key:
-        with torch.no_grad():
-            w = torch.cat([x.detach() for x in ws], dim=0) if len(ws) > 1 else ws[0].detach()
-            hit = (key, hip.pack_weight(w.float().contiguous()))
-        cache[names] = hit
-    return hit[1]
+    """bf16 [N, K] and [K, N] operand copies of one weight, or of several concatenated along N (packs.get)"""
+    return packs.get(mod, names)
 
 
 def _wqkv(at):
@@ -85,33 +76,11 @@ def _wqkv(at):
 
 def _pack_qkv(at):
     """bf16 operand copies of _wqkv(at)"""
-    if at._gqa_rows is None:
-        return _pack(at, "wqkv")
-    w = at.wqkv.weight
-    key = (w.data_ptr(), w._version)
-    hit = at.__dict__.get("_vt_pack_gqa")
-    if hit is None or hit[0] != key:
-        with torch.no_grad():
-            hit = (key, hip.pack_weight(w.detach().index_select(0, at._gqa_rows).float().contiguous()))
-        at.__dict__["_vt_pack_gqa"] = hit
-    return hit[1]
+    return packs.get(at, ("wqkv",), rows=at._gqa_rows)
 
 
 def _f32(t):
     return t if t.dtype == torch.float32 else t.float()
-
-
-def _rows64(*ts):
-    """the weight-gradient GEMMs contract over rows in steps of 64: zero-pad ragged row counts (never at the training shapes)"""
-    M = ts[0].shape[0]
-    if M % 64 == 0:
-        return ts
-    out = []
-    for t in ts:
-        z = torch.zeros((M + 63) // 64 * 64, t.shape[1], device=t.device, dtype=t.dtype)
-        z[:M].copy_(t)
-        out.append(z)
-    return out
 
 
 class _AttnBranch(torch.autograd.Function):
@@ -340,15 +309,7 @@ def _decode_fusion():
 
 def _pack_swiglu(ff):
     """bf16 [2I, D]: w3 and w1 interleaved in slabs of 8 + 8 rows, the operand layout of vt_decode_norm_linear(mode 1)"""
-    key = tuple((w.data_ptr(), w._version) for w in (ff.w3.weight, ff.w1.weight))
-    hit = ff.__dict__.get("_vt_pack_swiglu")
-    if hit is None or hit[0] != key:
-        with torch.no_grad():
-            I, K = ff.w1.weight.shape
-            w = torch.cat([ff.w3.weight.detach().reshape(I // 8, 8, K), ff.w1.weight.detach().reshape(I // 8, 8, K)], dim=1).reshape(2 * I, K)
-            hit = (key, w.to(torch.bfloat16).contiguous())
-        ff.__dict__["_vt_pack_swiglu"] = hit
-    return hit[1]
+    return packs.get(ff, ("w3", "w1"), interleave8=True)
 
 
 class LARP_AR(nn.Module, LocalPretrainedMixin):   # from_pretrained / save_pretrained: local directory, PyTorchModelHubMixin's layout (larp_ar.py:233)

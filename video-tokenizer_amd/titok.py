@@ -13,24 +13,20 @@ size keyword and hard-codes 16x128x128 clips, (4,8,8) patches, 1024 latent token
 `_geometry=` override exists for small parity tests), same `encode / decode / decode_indices / forward -> {'pred_frames'}`.
 
 One transformer layer (models/model_new/base/transformer.py:45-91) = 4 MFMA GEMMs + the LARP path's attention and
-LayerNorm kernels + the single-pass glue of csrc/vt_gated.hip, composed in `GatedLayer` (forward and hand-written
-backward; torch only owns tensors).  Mixed precision = autocast(bf16) as the reference trains: fp32 residual stream,
-bf16 GEMM operands with fp32 accumulation, fp32 LayerNorm statistics.  GPU tensors only; B * L must be a multiple of 64.
+LayerNorm kernels + the single-pass glue of csrc/vt_gated.hip, enqueued for the whole stack by the C++ engine of
+csrc/vt_gated_engine.hip (functional.GatedStack; torch only owns tensors).  Mixed precision = autocast(bf16) as the
+reference trains: fp32 residual stream, bf16 GEMM operands with fp32 accumulation, fp32 LayerNorm statistics.  GPU tensors only; B * L must be a multiple of 64.
 """
 import math
-import os
 
 import numpy as np
 import torch
 from torch import nn
 
-from . import hip
+from . import hip, packs
 from .fsq import FSQ
-from .functional import LayerNormRows, Linear as LinearFn, PatchEmbed as PatchEmbedFn, _pad64, rotary_block_stack
+from .functional import GatedStack, LayerNormRows, Linear as LinearFn, PatchEmbed as PatchEmbedFn, gated_params, rotary_block_stack
 from .registry import register
-
-import itertools
-_PACK_UID = itertools.count(1)   # identities of the modules that own packed weight copies (see ResidualAttentionBlock._identity)
 
 
 def get_model_dims(model_size="tiny", head_dim=64, mlp_ratio=4.0):
@@ -110,77 +106,6 @@ def rope_positions_unify(cond_tokens, in_tokens, grid):
     return np.concatenate([p0[:cond_tokens], p1], axis=0)
 
 
-def pack_layer_weights(w_qkv, w_out, w_fc1, w_fc2):
-    """bf16 [N, K] copies and [K, N] transposes of a layer's four matrices; fc2's contraction dim padded to a multiple of 64"""
-    with torch.no_grad():
-        return (*hip.pack_weight(w_qkv), *hip.pack_weight(w_out), *hip.pack_weight(w_fc1),
-                *hip.pack_weight(w_fc2, k_pad=_pad64(w_fc2.shape[1])))
-
-
-class GatedLayer(torch.autograd.Function):
-    """x -> (x + Attn(x) ; + ffd(.)) * scale for one layer of ResidualAttentionBlock (transformer.py:45-63, 20-29, 82-91)."""
-
-    @staticmethod
-    def forward(ctx, x, cos, sin, n_head, scale, packs, w_qkv, q_w, q_b, k_w, k_b, w_out, ln_w, ln_b, w_fc1, w_fc2):
-        hip.require_gpu(x, cos, sin, w_qkv, w_out, w_fc1, w_fc2)
-        B, L, D = x.shape
-        M = B * L
-        if M % 64 or D != 64 * n_head:
-            raise hip.HipError(f"GatedLayer: B * L = {M} must be a multiple of 64 and width {D} = 64 * heads")
-        inner = w_fc2.shape[1]
-        ipad = _pad64(inner)
-        x2 = x.contiguous().reshape(M, D).float()
-        xb = hip.cast_rows(x2)
-        if packs is None:                                            # bf16 operand copies (and their transposes for the dgrads)
-            packs = pack_layer_weights(w_qkv, w_out, w_fc1, w_fc2)
-        wqkv_b, wqkv_t, wout_b, wout_t, wfc1_b, wfc1_t, wfc2_b, wfc2_t = packs
-        qkvg = hip.gemm_nt(xb, wqkv_b, hip.EPI_BF16)
-        qkv = hip.qknorm_rope_fwd(qkvg, L, n_head, q_w, q_b, k_w, k_b, 1e-5, cos, sin)
-        o, lse = hip.attention_fwd(qkv, B, L, n_head, 64)
-        og = hip.sigmoid_gate_fwd(o, qkvg)
-        x1 = hip.gemm_nt(og, wout_b, hip.EPI_F32, residual=x2, round_bf16=True)
-        y, mean, rstd = hip.layernorm_fwd(x1, ln_w, ln_b, 1e-5)
-        h = hip.gemm_nt(y, wfc1_b, hip.EPI_BF16)
-        a = hip.geglu_fwd(h, lda=ipad)
-        out = hip.gemm_nt(a, wfc2_b, hip.EPI_F32, residual=x1, round_bf16=True)
-        if scale != 1.0:
-            out.mul_(scale)
-        ctx.save_for_backward(xb, qkvg, qkv, o, lse, og, x1, y, mean, rstd, h, a, cos, sin, q_w, k_w, ln_w, wqkv_t, wout_t, wfc1_t, wfc2_t)
-        ctx.geom = (B, L, D, n_head, scale, inner)
-        return out.reshape(B, L, D)
-
-    @staticmethod
-    def backward(ctx, dout):
-        xb, qkvg, qkv, o, lse, og, x1, y, mean, rstd, h, a, cos, sin, q_w, k_w, ln_w, wqkv_t, wout_t, wfc1_t, wfc2_t = ctx.saved_tensors
-        B, L, D, n_head, scale, inner = ctx.geom
-        M = B * L
-        dev = dout.device
-        d2 = dout.contiguous().reshape(M, D).float()
-        if scale != 1.0:
-            d2 = d2 * scale
-        # ffd backward
-        gb = hip.cast_rows(d2)
-        da = hip.gemm_nt(gb, wfc2_t, hip.EPI_BF16)                                   # [M, ipad]
-        dw_fc2 = torch.empty(D, a.shape[1], device=dev)
-        dh = hip.geglu_bwd(da, h)
-        dy = hip.gemm_nt(dh, wfc1_t, hip.EPI_BF16)
-        dw_fc1 = torch.empty(h.shape[1], D, device=dev)
-        dx1, dx1b, d_ln_w, d_ln_b, _ = hip.layernorm_bwd(dy, x1, ln_w, mean, rstd, dres=d2, want_dxsum=False)
-        # attention backward
-        dog = hip.gemm_nt(dx1b, wout_t, hip.EPI_BF16)
-        dw_out = torch.empty(D, D, device=dev)
-        dqkvg = torch.empty_like(qkvg)
-        d_o = hip.sigmoid_gate_bwd(dog, o, qkvg, dqkvg)
-        dqkv = hip.attention_bwd(qkv, o, d_o, lse, B, L, n_head, 64)
-        dq_w, dq_b, dk_w, dk_b = hip.qknorm_rope_bwd(qkvg, dqkv, L, n_head, q_w, k_w, 1e-5, cos, sin, dqkvg)
-        dx = hip.gemm_nt(dqkvg, wqkv_t, hip.EPI_F32, residual=dx1, round_bf16=True)
-        dw_qkv = torch.empty(4 * D, D, device=dev)
-        hip.gemm_tn_grouped([dict(A=gb, B=a, out=dw_fc2), dict(A=dh, B=y, out=dw_fc1), dict(A=dx1b, B=og, out=dw_out),
-                             dict(A=dqkvg, B=xb, out=dw_qkv)])
-        return (dx.reshape(B, L, D), None, None, None, None, None, dw_qkv, dq_w, dq_b, dk_w, dk_b, dw_out, d_ln_w, d_ln_b, dw_fc1,
-                dw_fc2[:, :inner].contiguous())
-
-
 class ConvTransposePatch(torch.autograd.Function):
     """nn.ConvTranspose3d(width, C, kernel = stride = (pt, p, p)) on a token grid (blocks.py:116-147): one GEMM into patch
     rows (c, dt, dy, dx) + the LARP path's unpatchify scatter; bf16-rounded output like the conv under autocast."""
@@ -218,7 +143,7 @@ class ConvTransposePatch(torch.autograd.Function):
 
 class GEGLU(nn.Module):
     """transformer.py:11-17; parameterless -- it keeps the reference's Sequential indices (ffd_layer.{i}.{0,1,3}); the
-    arithmetic runs fused inside GatedLayer (vt_geglu_fwd / vt_geglu_bwd)"""
+    arithmetic runs inside the stack engine (vt_geglu_fwd / vt_geglu_bwd)"""
 
     def forward(self, x):
         raise NotImplementedError("GEGLU runs inside ResidualAttentionBlock's fused layer")
@@ -230,7 +155,7 @@ def ffd(dim, mult=4, mult_of=32):
 
 
 class Attn(nn.Module):
-    """transformer.py:32-43 (parameters; the forward is GatedLayer)"""
+    """transformer.py:32-43 (parameters; the forward is functional.GatedStack's, for the whole stack)"""
 
     def __init__(self, dim, heads):
         super().__init__()
@@ -250,53 +175,13 @@ class ResidualAttentionBlock(nn.Module):
         self.num_layer, self.heads = num_layer, heads
         self.attn_layer = nn.Sequential(*[Attn(embed_dim, heads) for _ in range(num_layer)])
         self.ffd_layer = nn.Sequential(*[ffd(embed_dim, mlp_ratio) for _ in range(num_layer)])
-        self._pack_cache = {}
-        self._vt_epoch = 0
-
-    def _identity(self):
-        """(unique id of THIS module object, invalidation epoch): part of every pack key.  Parameter addresses and `_version`
-        counters alone do not identify a weight: the caching allocator hands a second model of the same geometry the addresses of
-        a deleted first one, and freshly initialised parameters all carry the same version.  The id is re-drawn after
-        copy.deepcopy (the copy's `__dict__` names the original as owner)."""
-        d = self.__dict__
-        if d.get("_vt_uid_owner") != id(self):
-            d["_vt_uid"], d["_vt_uid_owner"] = next(_PACK_UID), id(self)
-        return (d["_vt_uid"], self._vt_epoch)
-
-    def invalidate_packs(self):
-        """call after writing weights through `.data` / under no_grad in a way that does not bump `_version` (`p.data.copy_`)"""
-        self._vt_epoch += 1
-        self._pack_cache.clear()
-
-    def _packs(self, i):
-        """the layer's bf16 operand copies, re-made only when a weight changed (optimizer step, load_state_dict, .to())"""
-        at, ff = self.attn_layer[i], self.ffd_layer[i]
-        ws = (at.to_qkv.weight, at.out_proj.weight, ff[1].weight, ff[3].weight)
-        key = (self._identity(),) + tuple((w.data_ptr(), w._version) for w in ws)
-        hit = self._pack_cache.get(i)
-        if hit is None or hit[0] != key:
-            hit = (key, pack_layer_weights(*ws))
-            self._pack_cache[i] = hit
-        return hit[1]
 
     def forward(self, x, freqs):
-        """the whole stack as one engine call per direction (functional.GatedStack -> vt_gated_stack_forward / _backward).
-        VT_GATED_PYTHON=1 selects the round-1 composition of one autograd Function per layer instead (A/B and tests)."""
+        """the whole stack as one engine call per direction (functional.GatedStack -> vt_gated_stack_forward / _backward); the engine keeps
+        bf16 copies of the four matrices of every layer in its workspace, re-made when the pack key changes"""
         cos, sin = freqs
-        if os.environ.get("VT_GATED_PYTHON") == "1":
-            for i in range(self.num_layer):
-                at, ff = self.attn_layer[i], self.ffd_layer[i]
-                x = GatedLayer.apply(x, cos, sin, self.heads, 1.0 / math.sqrt(i + 1), self._packs(i), at.to_qkv.weight, at.q_norm.weight, at.q_norm.bias,
-                                     at.k_norm.weight, at.k_norm.bias, at.out_proj.weight, ff[0].weight, ff[0].bias, ff[1].weight, ff[3].weight)
-            return x
-        from .functional import GatedStack
-        params, key = [], [self._identity()]
-        for i in range(self.num_layer):
-            at, ff = self.attn_layer[i], self.ffd_layer[i]
-            params += [at.to_qkv.weight, at.q_norm.weight, at.q_norm.bias, at.k_norm.weight, at.k_norm.bias, at.out_proj.weight, ff[0].weight, ff[0].bias,
-                       ff[1].weight, ff[3].weight]
-            key += [(w.data_ptr(), w._version) for w in (at.to_qkv.weight, at.out_proj.weight, ff[1].weight, ff[3].weight)]
-        return GatedStack.apply(x, cos, sin, self.heads, tuple(key), *params)
+        params = gated_params(self)
+        return GatedStack.apply(x, cos, sin, self.heads, packs.pack_key(self, [p for p in params if p.dim() == 2]), *params)
 
 
 class SimpleMlp(nn.Module):
