@@ -233,6 +233,27 @@ int vt_attention_cross_bwd(const void* q, int64_t q_rs, const void* k, int64_t k
                            const void* dO, const float* lse2, int32_t B, int32_t Lq, int32_t Lk, int32_t H, int32_t hd, void* dq,
                            int64_t dq_rs, void* dk, int64_t dk_rs, void* dv, int64_t dv_rs, float* delta_ws, vtStream stream);
 
+/* Packed variable-length attention with grouped KV heads (the Attn layer of models/model_titok/base/transformer.py:32-62, which calls
+ * flash_attn_varlen_func): n_seq sequences lie one behind the other in the M = cu_seqlens[n_seq] rows of every operand, sequence b is
+ * rows cu_seqlens[b] .. cu_seqlens[b+1]-1 and attends only inside itself.  q is a view [M, 64 Hq], k and v views [M, 64 Hkv] of bf16
+ * buffers with row strides q_rs / k_rs / v_rs (the three column blocks of one [M, 64 (Hq + 2 Hkv)] projection are the main caller);
+ * Hq % Hkv == 0 and query head h reads KV head h / (Hq / Hkv) (repeat_interleave, flash-attn's convention).  o / dO bf16 dense
+ * [M, 64 Hq]; lse2 and delta_ws fp32 [Hq, M]; dq [M, 64 Hq], dk and dv [M, 64 Hkv] with their own row strides.  Scale 64^-0.5, no mask.
+ * cu_seqlens_host is a HOST array of n_seq + 1 entries, read before the call returns: it is validated here (cu[0] == 0, strictly
+ * increasing -- an empty sequence is refused --, cu[n_seq] == M, 1 <= n_seq <= VT_VARLEN_MAX_SEQ) and travels to the kernels by value
+ * in their arguments, so no kernel reads a boundary from device memory and the launch can be captured in a graph.  Strides and
+ * alignment as for vt_attention_cross_* (VT_ERR_INVALID + vt_last_error otherwise).  The grid is exactly sum_b ceil(L_b / 128) workgroups
+ * per head.  dK/dV sums the query heads of a group in ascending order inside one workgroup: no atomics, the same bits on every run.  The
+ * kernels and tile code of vt_attention_cross_*: with one sequence and Hq == Hkv the results are bit-identical to B = 1, Lq = Lk = M. */
+#define VT_VARLEN_MAX_SEQ 64
+int vt_attention_varlen_fwd(const void* q, int64_t q_rs, const void* k, int64_t k_rs, const void* v, int64_t v_rs,
+                            const int32_t* cu_seqlens_host, int32_t n_seq, int32_t M, int32_t Hq, int32_t Hkv, int32_t hd, void* o, float* lse2,
+                            vtStream stream);
+int vt_attention_varlen_bwd(const void* q, int64_t q_rs, const void* k, int64_t k_rs, const void* v, int64_t v_rs, const void* o,
+                            const void* dO, const float* lse2, const int32_t* cu_seqlens_host, int32_t n_seq, int32_t M, int32_t Hq,
+                            int32_t Hkv, int32_t hd, void* dq, int64_t dq_rs, void* dk, int64_t dk_rs, void* dv, int64_t dv_rs, float* delta_ws,
+                            vtStream stream);
+
 /* ------------------------------------------------------------------------------------------
  * Vector quantisation (SimpleVectorQuantizer.forward, models/bottleneck.py:262-324).
  *   mode 0: stochastic=False  argmin(|z|^2+|e|^2-2z.e)           (:282-290)
@@ -364,6 +385,23 @@ size_t vt_qknorm_rope_bwd_workspace_bytes(void);
 int vt_qknorm_rope_bwd(const void* qkvg, const void* dqkv, int64_t M, int32_t L, int32_t H, const float* q_w, const float* k_w,
                        float eps, const float* cos_tab, const float* sin_tab, void* dqkvg, float* dq_w, float* dq_b, float* dk_w,
                        float* dk_b, void* workspace, vtStream stream);
+/* The grouped-projection twin of vt_qknorm_rope_* for the packed variable-length layer (Attn of models/model_titok/base/transformer.py:32-62;
+ * csrc/vt_varlen.hip).  qkv bf16 [M, 64 (Hq + 2 Hkv)] (row stride in_rs), columns q | k | v = to_qkv(x) of a packed batch of M rows;
+ * qkv_out the same layout (row stride out_rs): every q head gets LayerNorm_64 with q_w / q_b, every k head with k_w / k_b, both are then
+ * rotated, v is copied.  Row m uses table row m: cos_tab / sin_tab are fp32 [M, 32], there is no period.  The backward takes the gradient
+ * of qkv_out (dqkv_out, row stride g_rs, what vt_attention_varlen_bwd wrote) and writes the gradient of qkv in the same layout (dqkv, row
+ * stride d_rs); dq_w, dq_b, dk_w, dk_b fp32 [64] each (any may be NULL) through fixed-order per-workgroup partials in a workspace of
+ * vt_qknorm_rope_gqa_bwd_workspace_bytes().  Hq % Hkv == 0; strides >= 64 (Hq + 2 Hkv) and multiples of 8; buffers and tables 16-byte
+ * aligned (VT_ERR_INVALID + vt_last_error otherwise).  Columns outside the three blocks and rows past M are neither read nor written.
+ * The same kernels as vt_qknorm_rope_*: with Hq == Hkv, in_rs = 4D and out_rs = 3D the output is bit-identical to vt_qknorm_rope_fwd
+ * called with L = M, and likewise the gradients to vt_qknorm_rope_bwd. */
+int vt_qknorm_rope_gqa_fwd(const void* qkv, int64_t in_rs, int64_t M, int32_t Hq, int32_t Hkv, const float* q_w, const float* q_b,
+                           const float* k_w, const float* k_b, float eps, const float* cos_tab, const float* sin_tab, void* qkv_out,
+                           int64_t out_rs, vtStream stream);
+size_t vt_qknorm_rope_gqa_bwd_workspace_bytes(void);
+int vt_qknorm_rope_gqa_bwd(const void* qkv, int64_t in_rs, const void* dqkv_out, int64_t g_rs, int64_t M, int32_t Hq, int32_t Hkv,
+                           const float* q_w, const float* k_w, float eps, const float* cos_tab, const float* sin_tab, void* dqkv, int64_t d_rs,
+                           float* dq_w, float* dq_b, float* dk_w, float* dk_b, void* workspace, vtStream stream);
 int vt_sigmoid_gate_fwd(const void* o, const void* qkvg, int64_t M, int32_t D, void* og, vtStream stream);
 int vt_sigmoid_gate_bwd(const void* dog, const void* o, const void* qkvg, int64_t M, int32_t D, void* d_o, void* dqkvg, vtStream stream);
 /* the same pair with the gate at any column offset and row stride (gate / dgate point at the first gate column of row 0; strides

@@ -38,6 +38,7 @@ from .larp_ar import LARP_AR  # noqa: F401
 from .loss import TransformerDiscriminator, VQLPIPSWithDiscriminator  # noqa: F401
 from .fsq import FSQ  # noqa: F401
 from . import design  # noqa: F401
+from . import varlen  # noqa: F401
 from .design import (AutoEncoder, CrossAttention, Encoder, FirstFrameEncoder, LearnedQueryTokens, RMSNorm, SelfAttention,  # noqa: F401
                      TransformerBlock, TransformerStack, UnifiedDecoder)
 

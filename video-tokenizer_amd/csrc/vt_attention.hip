@@ -8,6 +8,9 @@
 // three pointers with a row stride each, Lq query rows and Lk key rows per batch; o / dO [B, Lq, H, 64], lse2 / delta [B, H, Lq].
 // The same kernels and tile code: a packed launch is the special case q = qkv, k = q + D, v = k + D, every stride 3D, Lq = Lk,
 // which the packed instantiations know at compile time (one stride register, one set of staging offsets) and CROSS ones do not.
+// Variable-length launches (vt_attention_varlen_*; Attn of models/model_titok/base/transformer.py:32-62, flash_attn_varlen_func): n sequences
+// packed one behind the other in [M, ...] operands, Hq query heads over Hkv KV heads, lse2 / delta [Hq, M].  Again the same kernels and tile
+// code behind a third address computation (varlen_head_ptrs): a sequence is a batch of one that starts at any row.
 //
 // Common skeleton (one workgroup = 4 waves, each wave owns 32 "stationary" rows held in registers as
 // MFMA B operands; 64-row "streaming" tiles are staged global -> LDS with 16-B global_load_lds,
@@ -50,34 +53,91 @@ struct AttnGrads {
     int64_t dq_rs, dk_rs, dv_rs;
 };
 struct HeadPtrs {
-    int b, h, blk;
+    int blk;
     int Lq, Lk;
+    int hq, hkv;                     // head columns of q / dq / o and of k / v / dk / dv (the same head unless the launch is grouped)
+    int group;                       // query heads hq .. hq + group - 1 share the KV head: the dK/dV workgroup sweeps them all (1 unless grouped)
+    int64_t qrow, krow;              // first row of the workgroup's batch (sequence) in q / dq and in k / v / dk / dv
     int64_t q_rs, k_rs, v_rs, ors;   // row strides (elements) of q, k, v and of o / dO [B, Lq, H, HD]
+    int64_t orow;                    // first row of the batch (sequence) in o / dO, which hold the kept queries only
+    int64_t st_off, st_hs;           // index of (first query row, head hq) in lse2 / delta, and the distance between two heads there
     const bf16_t *qb, *kb, *vb;
 };
 template <int HD, bool CROSS>
-__device__ __forceinline__ HeadPtrs head_ptrs(const AttnOps& a, int H, int nblk) {
+__device__ __forceinline__ HeadPtrs head_ptrs(const AttnOps& a, int H, int nblk, int q_begin) {
     HeadPtrs p;
     const int sid = xcd_remap(blockIdx.x, gridDim.x);
     const int bh = sid / nblk;
     p.blk = sid - bh * nblk;
-    p.b = bh / H;
-    p.h = bh % H;
+    const int b = bh / H, h = bh % H;
+    p.hq = p.hkv = h;
+    p.group = 1;
     p.ors = (int64_t)H * HD;
     p.Lq = a.Lq;
+    p.qrow = (int64_t)b * p.Lq;
+    p.orow = (int64_t)b * (p.Lq - q_begin);
+    p.st_off = ((int64_t)b * H + h) * p.Lq;
+    p.st_hs = p.Lq;
     if constexpr (CROSS) {
         p.Lk = a.Lk;
+        p.krow = (int64_t)b * p.Lk;
         p.q_rs = a.q_rs, p.k_rs = a.k_rs, p.v_rs = a.v_rs;
-        p.qb = a.q + (int64_t)p.b * p.Lq * p.q_rs + (int64_t)p.h * HD;
-        p.kb = a.k + (int64_t)p.b * p.Lk * p.k_rs + (int64_t)p.h * HD;
-        p.vb = a.v + (int64_t)p.b * p.Lk * p.v_rs + (int64_t)p.h * HD;
+        p.qb = a.q + p.qrow * p.q_rs + (int64_t)h * HD;
+        p.kb = a.k + p.krow * p.k_rs + (int64_t)h * HD;
+        p.vb = a.v + p.krow * p.v_rs + (int64_t)h * HD;
     } else {
         p.Lk = p.Lq;
+        p.krow = p.qrow;
         p.q_rs = p.k_rs = p.v_rs = (int64_t)3 * H * HD;
-        p.qb = a.q + (int64_t)p.b * p.Lq * p.q_rs + (int64_t)p.h * HD;
+        p.qb = a.q + p.qrow * p.q_rs + (int64_t)h * HD;
         p.kb = p.qb + p.ors;
         p.vb = p.kb + p.ors;
     }
+    return p;
+}
+
+// Packed variable-length launches (vt_attention_varlen_*): n sequences of cu[b+1] - cu[b] rows each, one behind the other in the
+// same [M, ...] operands; Hq query heads over Hkv KV heads.  The boundaries and the prefix of 128-row blocks per sequence are KERNEL
+// ARGUMENTS (the host validated them; nothing is read from device memory that a caller could leave stale), so the grid is exactly
+// blk[n] * heads workgroups and each finds its (head, sequence, block) by a scalar bisection of blk[].
+struct SeqTable {
+    int n, total;                    // sequences; total = blk[n]
+    int cu[VT_VARLEN_MAX_SEQ + 1];   // first row of sequence b; cu[n] = M
+    int blk[VT_VARLEN_MAX_SEQ + 1];  // 128-row blocks before sequence b
+};
+// KV = false: the forward and dQ, one workgroup per (query head, sequence, 128 queries); KV = true: dK/dV, one per (KV head, sequence,
+// 128 keys), hq = the first query head of its group.  A sequence is a "batch" of one whose rows start at cu[b]: the tile code clamps
+// loads to its last row and masks stores past it exactly as at the end of a dense batch.  Everything the bisection yields is
+// wave-uniform and goes through readfirstlane, because the full-tile stagers take the row base as a scalar ("s") operand.
+template <int HD, bool KV>
+__device__ __forceinline__ HeadPtrs varlen_head_ptrs(const AttnOps& a, const SeqTable& tab, int Hq, int Hkv, int M) {
+    HeadPtrs p;
+    const int sid = xcd_remap(blockIdx.x, gridDim.x);
+    const int h = sid / tab.total;
+    const int gb = sid - h * tab.total;
+    int lo = 0, hi = tab.n;          // blk[lo] <= gb < blk[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (tab.blk[mid] <= gb) lo = mid;
+        else hi = mid;
+    }
+    const int b = __builtin_amdgcn_readfirstlane(lo);
+    const int row0 = __builtin_amdgcn_readfirstlane(tab.cu[b]);
+    const int L = __builtin_amdgcn_readfirstlane(tab.cu[b + 1] - row0);
+    p.blk = __builtin_amdgcn_readfirstlane(gb - tab.blk[b]);
+    p.group = Hq / Hkv;
+    p.hq = __builtin_amdgcn_readfirstlane(KV ? h * p.group : h);
+    p.hkv = __builtin_amdgcn_readfirstlane(KV ? h : h / p.group);
+    p.Lq = p.Lk = L;
+    p.qrow = p.krow = row0;
+    p.ors = (int64_t)Hq * HD;
+    p.q_rs = a.q_rs, p.k_rs = a.k_rs, p.v_rs = a.v_rs;
+    p.orow = row0;
+    p.st_off = (int64_t)p.hq * M + row0;     // lse2 / delta [Hq, M]
+    p.st_hs = M;
+    p.qb = a.q + (int64_t)row0 * p.q_rs + (int64_t)p.hq * HD;
+    p.kb = a.k + (int64_t)row0 * p.k_rs + (int64_t)p.hkv * HD;
+    p.vb = a.v + (int64_t)row0 * p.v_rs + (int64_t)p.hkv * HD;
     return p;
 }
 // first gradient row of the workgroup's (batch, head) in dq / dk / dv
@@ -86,12 +146,12 @@ __device__ __forceinline__ AttnGrads grad_ptrs(const AttnGrads& g, const HeadPtr
     AttnGrads r;
     if constexpr (CROSS) {
         r.dq_rs = g.dq_rs, r.dk_rs = g.dk_rs, r.dv_rs = g.dv_rs;
-        r.dq = g.dq + (int64_t)hp.b * hp.Lq * r.dq_rs + (int64_t)hp.h * HD;
-        r.dk = g.dk + (int64_t)hp.b * hp.Lk * r.dk_rs + (int64_t)hp.h * HD;
-        r.dv = g.dv + (int64_t)hp.b * hp.Lk * r.dv_rs + (int64_t)hp.h * HD;
+        r.dq = g.dq + hp.qrow * r.dq_rs + (int64_t)hp.hq * HD;
+        r.dk = g.dk + hp.krow * r.dk_rs + (int64_t)hp.hkv * HD;
+        r.dv = g.dv + hp.krow * r.dv_rs + (int64_t)hp.hkv * HD;
     } else {
         r.dq_rs = r.dk_rs = r.dv_rs = hp.q_rs;
-        r.dq = g.dq + (int64_t)hp.b * hp.Lq * hp.q_rs + (int64_t)hp.h * HD;
+        r.dq = g.dq + hp.qrow * hp.q_rs + (int64_t)hp.hq * HD;
         r.dk = r.dq + hp.ors;
         r.dv = r.dk + hp.ors;
     }
@@ -223,19 +283,19 @@ __device__ __forceinline__ void fwd_tile(unsigned kl, unsigned vl, const TileAdd
 // CAUSAL (the AR consumer, models/larp_ar.py:186-190 `is_causal=True`): query q attends keys 0..q.  A workgroup stops at the last
 // tile its 128 queries can see; per wave a tile is plain (every key <= every query of the wave), masked (fwd_tile<TAIL> with
 // the per-lane limit q + 1 in place of L) or skipped.
-template <int HD, bool CAUSAL = false, bool CROSS = false>
-__global__ __launch_bounds__(256, CAUSAL ? 3 : 4) void attn_fwd_kernel(const AttnOps ops, bf16_t* __restrict__ o, float* __restrict__ lse2,
-                                                           int H, int nblk, float scale_log2e, int q_begin) {
+// The three kernel bodies ask `heads()` for the workgroup's HeadPtrs: the dense and cross kernels answer with head_ptrs, the packed
+// variable-length ones with varlen_head_ptrs (CROSS = true: separate strides); the tile code below does not know which.
+template <int HD, bool CAUSAL, bool CROSS, class Heads>
+__device__ __forceinline__ void attn_fwd_body(Heads&& heads, bf16_t* __restrict__ o, float* __restrict__ lse2, float scale_log2e, int q_begin) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int half = lane >> 5;
-    const HeadPtrs hp = head_ptrs<HD, CROSS>(ops, H, nblk);
+    const HeadPtrs hp = heads();
     const int Lq = hp.Lq, Lk = hp.Lk;
     // queries q_begin .. Lq-1 only (q_begin > 0: the last block of a stack, whose other output rows nobody reads); their
     // outputs go to a COMPACT o [B, Lq - q_begin, H, HD]; keys are always all Lk rows; lse2 keeps the full [B, H, Lq] index
     const int q0 = q_begin + hp.blk * 128 + wave * 32;
-    const int Lo = Lq - q_begin;
 
     constexpr int TILE = AG<HD>::TILE, KS = AG<HD>::KS, DT = AG<HD>::DT;
     bf16x8 qf[KS];
@@ -276,8 +336,17 @@ __global__ __launch_bounds__(256, CAUSAL ? 3 : 4) void attn_fwd_kernel(const Att
     const float ltot = lsum + __shfl_xor(lsum, 32);
     const int q = q0 + (lane & 31);
     const bool ok = q < Lq;
-    store_own<DT>(oacc, 1.0f / ltot, o + (int64_t)hp.b * Lo * hp.ors + (int64_t)hp.h * HD, hp.ors, q - q_begin, ok, half);
-    if (ok && half == 0) lse2[((int64_t)hp.b * H + hp.h) * Lq + q] = m + __builtin_amdgcn_logf(ltot);  // v_log_f32 = log2
+    store_own<DT>(oacc, 1.0f / ltot, o + hp.orow * hp.ors + (int64_t)hp.hq * HD, hp.ors, q - q_begin, ok, half);
+    if (ok && half == 0) lse2[hp.st_off + q] = m + __builtin_amdgcn_logf(ltot);  // v_log_f32 = log2
+}
+template <int HD, bool CAUSAL = false, bool CROSS = false>
+__global__ __launch_bounds__(256, CAUSAL ? 3 : 4) void attn_fwd_kernel(const AttnOps ops, bf16_t* __restrict__ o, float* __restrict__ lse2,
+                                                           int H, int nblk, float scale_log2e, int q_begin) {
+    attn_fwd_body<HD, CAUSAL, CROSS>([&]() __attribute__((always_inline)) { return head_ptrs<HD, CROSS>(ops, H, nblk, q_begin); }, o, lse2, scale_log2e, q_begin);
+}
+__global__ __launch_bounds__(256, 4) void attn_varlen_fwd_kernel(const AttnOps ops, const SeqTable tab, bf16_t* __restrict__ o,
+                                                                 float* __restrict__ lse2, int Hq, int Hkv, int M, float scale_log2e) {
+    attn_fwd_body<64, false, true>([&]() __attribute__((always_inline)) { return varlen_head_ptrs<64, false>(ops, tab, Hq, Hkv, M); }, o, lse2, scale_log2e, 0);
 }
 
 template <int HD, bool TAIL>
@@ -321,16 +390,15 @@ __device__ __forceinline__ void dq_tile(unsigned kl, unsigned vl, const TileAddr
 // delta[b,h,q] = sum_d dO[b,q,h,d] * O[b,q,h,d] for its own rows (both operands are one 16-B load per k-step away) and
 // leaves it in `delta` for the dK/dV kernel, which is launched behind this one.
 // ------------------------------------------------------------------------------------------------
-template <int HD, bool CAUSAL = false, bool CROSS = false>
-__global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(const AttnOps ops, const bf16_t* __restrict__ o,
-                                                              const bf16_t* __restrict__ dO, const float* __restrict__ lse2,
-                                                              float* __restrict__ delta, const AttnGrads grads, int H, int nblk,
-                                                              float scale, float scale_log2e, int q_begin) {
+template <int HD, bool CAUSAL, bool CROSS, class Heads>
+__device__ __forceinline__ void attn_bwd_dq_body(Heads&& heads, const bf16_t* __restrict__ o, const bf16_t* __restrict__ dO,
+                                                 const float* __restrict__ lse2, float* __restrict__ delta, const AttnGrads grads, float scale,
+                                                 float scale_log2e, int q_begin) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int half = lane >> 5;
-    const HeadPtrs hp = head_ptrs<HD, CROSS>(ops, H, nblk);
+    const HeadPtrs hp = heads();
     const int Lq = hp.Lq, Lk = hp.Lk;
     const int q0 = q_begin + hp.blk * 128 + wave * 32;   // kept queries only; o / dO are compact [B, Lq - q_begin, H, HD]
     const int Lo = Lq - q_begin;
@@ -340,18 +408,18 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(const AttnOps ops, 
     constexpr int TILE = AG<HD>::TILE, KS = AG<HD>::KS, DT = AG<HD>::DT;
     bf16x8 qf[KS], dof[KS];
     load_own<KS>(hp.qb, hp.q_rs, q0, Lq, lane, qf);
-    load_own<KS>(dO + (int64_t)hp.b * Lo * hp.ors + (int64_t)hp.h * HD, hp.ors, q0 - q_begin, Lo, lane, dof);
-    const float my_lse = lse2[((int64_t)hp.b * H + hp.h) * Lq + qc];
+    load_own<KS>(dO + hp.orow * hp.ors + (int64_t)hp.hq * HD, hp.ors, q0 - q_begin, Lo, lane, dof);
+    const float my_lse = lse2[hp.st_off + qc];
     float my_delta = 0.f;
     {
         bf16x8 of[KS];
-        load_own<KS>(o + (int64_t)hp.b * Lo * hp.ors + (int64_t)hp.h * HD, hp.ors, q0 - q_begin, Lo, lane, of);
+        load_own<KS>(o + hp.orow * hp.ors + (int64_t)hp.hq * HD, hp.ors, q0 - q_begin, Lo, lane, of);
 #pragma unroll
         for (int s = 0; s < KS; ++s)
 #pragma unroll
             for (int j = 0; j < 8; ++j) my_delta += bf2f(of[s][j]) * bf2f(dof[s][j]);
         my_delta += __shfl_xor(my_delta, 32);   // the two lane halves hold the two halves of every 16-wide k-step
-        if (q < Lq && half == 0) delta[((int64_t)hp.b * H + hp.h) * Lq + q] = my_delta;
+        if (q < Lq && half == 0) delta[hp.st_off + q] = my_delta;
     }
 
     f32x16 dq[DT];
@@ -391,6 +459,19 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(const AttnOps ops, 
     });
     const AttnGrads g = grad_ptrs<HD, CROSS>(grads, hp);
     store_own<DT>(dq, scale, g.dq, g.dq_rs, q, q < Lq, half);
+}
+template <int HD, bool CAUSAL = false, bool CROSS = false>
+__global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(const AttnOps ops, const bf16_t* __restrict__ o,
+                                                              const bf16_t* __restrict__ dO, const float* __restrict__ lse2,
+                                                              float* __restrict__ delta, const AttnGrads grads, int H, int nblk,
+                                                              float scale, float scale_log2e, int q_begin) {
+    attn_bwd_dq_body<HD, CAUSAL, CROSS>([&]() __attribute__((always_inline)) { return head_ptrs<HD, CROSS>(ops, H, nblk, q_begin); }, o, dO, lse2, delta, grads, scale, scale_log2e, q_begin);
+}
+__global__ __launch_bounds__(256, 3) void attn_varlen_bwd_dq_kernel(const AttnOps ops, const SeqTable tab, const bf16_t* __restrict__ o,
+                                                                    const bf16_t* __restrict__ dO, const float* __restrict__ lse2,
+                                                                    float* __restrict__ delta, const AttnGrads grads, int Hq, int Hkv, int M,
+                                                                    float scale, float scale_log2e) {
+    attn_bwd_dq_body<64, false, true>([&]() __attribute__((always_inline)) { return varlen_head_ptrs<64, false>(ops, tab, Hq, Hkv, M); }, o, dO, lse2, delta, grads, scale, scale_log2e, 0);
 }
 
 // one 64-query tile of the dK/dV sweep.  LDS buffer: Q tile | dO tile | lse2[64] | delta[64]
@@ -453,23 +534,22 @@ __device__ __forceinline__ void dkv_tile(unsigned qt_l, unsigned lse_a, const Ti
 // ------------------------------------------------------------------------------------------------
 // dK, dV: own rows = keys; streams Q and dO tiles (both row reads and transposed reads) + lse2/delta
 // ------------------------------------------------------------------------------------------------
-template <int HD, bool CAUSAL = false, bool CROSS = false>
-__global__ __launch_bounds__(256, CAUSAL ? 2 : 3) void attn_bwd_dkv_kernel(const AttnOps ops, const bf16_t* __restrict__ dO,
-                                                               const float* __restrict__ lse2, const float* __restrict__ delta,
-                                                               const AttnGrads grads, int H, int nblk, float scale, float scale_log2e,
-                                                               int q_begin) {
+// GROUPED (the variable-length launches): the workgroup's keys belong to one KV head that hp.group query heads read.  It sweeps those
+// heads in ascending order, ascending query tiles within a head, into the same fp32 accumulators and rounds once: no atomics, no sum
+// across workgroups, the same bits on every run; with one head per group this is the plain sweep.
+template <int HD, bool CAUSAL, bool CROSS, bool GROUPED, class Heads>
+__device__ __forceinline__ void attn_bwd_dkv_body(Heads&& heads, const bf16_t* __restrict__ dO, const float* __restrict__ lse2,
+                                                  const float* __restrict__ delta, const AttnGrads grads, float scale, float scale_log2e,
+                                                  int q_begin) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int half = lane >> 5;
-    const HeadPtrs hp = head_ptrs<HD, CROSS>(ops, H, nblk);
+    const HeadPtrs hp = heads();
     const int64_t rs = hp.q_rs, ors = hp.ors;
     const int Lq = hp.Lq, Lk = hp.Lk;
     // query tiles from q_begin on (a multiple of 64; the rows before it got no gradient), dO compact [B, Lq - q_begin, H, HD]
     const int Lo = Lq - q_begin;
-    const bf16_t* dob = dO + (int64_t)hp.b * Lo * ors + (int64_t)hp.h * HD;
-    const float* lse_b = lse2 + ((int64_t)hp.b * H + hp.h) * Lq;
-    const float* del_b = delta + ((int64_t)hp.b * H + hp.h) * Lq;
     const int k0 = hp.blk * 128 + wave * 32;
     const int key = k0 + (lane & 31);
 
@@ -495,37 +575,75 @@ __global__ __launch_bounds__(256, CAUSAL ? 2 : 3) void attn_bwd_dkv_kernel(const
     stage_offsets<HD>(rs, tid, qoff);
     stage_offsets<HD>(ors, tid, dooff);
     const int nfull_q = Lq / 64;       // query tiles without a ragged row
-    auto stage = [&](int t, int buf) __attribute__((always_inline)) {
-        const unsigned base = sbase + buf * BUF;
-        if (t < nfull_q) {
-            stage64_full<HD>(hp.qb + (int64_t)t * 64 * rs, qoff, base, wave);
-            stage64_full<HD>(dob + ((int64_t)t * 64 - q_begin) * ors, dooff, base + TILE, wave);
-        } else {
-            stage64<HD>(hp.qb, rs, t * 64, Lq, base, tid, wave);
-            stage64<HD>(dob, ors, t * 64 - q_begin, Lo, base + TILE, tid, wave);
-        }
-        if (wave < 2) {  // wave 0: lse2[64], wave 1: delta[64] by 4-byte LDS-DMA (rows past Lq clamped; masked at use)
-            int qq = t * 64 + lane;
-            qq = qq < Lq ? qq : Lq - 1;
-            glds4_asm((wave == 0 ? lse_b : del_b) + qq, base + 2 * TILE + wave * 256);
-        }
-    };
     // CAUSAL: query tiles before the workgroup's first key contribute nothing (every query < every key)
     const int t0 = CAUSAL ? max(q_begin >> 6, (hp.blk * 128) >> 6) : q_begin >> 6;
-    stage(t0, 0);
-    pin_loaded(kf);
-    pin_loaded(vf);
-    dma_drain();
-    __syncthreads();
+    auto sweep_head = [&](int j) __attribute__((always_inline)) {   // query head hq + j: its Q / dO columns and its lse2 / delta row
+        const bf16_t* qb = hp.qb + j * HD;
+        const bf16_t* dob = dO + hp.orow * ors + (int64_t)hp.hq * HD + j * HD;
+        const float* lse_b = lse2 + hp.st_off + j * hp.st_hs;
+        const float* del_b = delta + hp.st_off + j * hp.st_hs;
+        // GROUPED: everything a ragged tile derives from the sequence length (clamped lane addresses, 32 row masks) is the same for every
+        // head; hoisted out of the head loop it would stay live through every tile body (53 SGPR spills).  One opaque copy of the length per
+        // head, used by everything below, keeps it inside the head.
+        int Lq_h = Lq, Lo_h = Lo;
+        if constexpr (GROUPED) {
+            asm volatile("" : "+s"(Lq_h));
+            Lo_h = Lq_h - q_begin;
+        }
+        auto stage = [&](int t, int buf) __attribute__((always_inline)) {
+            const unsigned base = sbase + buf * BUF;
+            if (t < nfull_q) {
+                stage64_full<HD>(qb + (int64_t)t * 64 * rs, qoff, base, wave);
+                stage64_full<HD>(dob + ((int64_t)t * 64 - q_begin) * ors, dooff, base + TILE, wave);
+            } else {
+                stage64<HD>(qb, rs, t * 64, Lq_h, base, tid, wave);
+                stage64<HD>(dob, ors, t * 64 - q_begin, Lo_h, base + TILE, tid, wave);
+            }
+            if (wave < 2) {  // wave 0: lse2[64], wave 1: delta[64] by 4-byte LDS-DMA (rows past Lq clamped; masked at use)
+                int qq = t * 64 + lane;
+                qq = qq < Lq_h ? qq : Lq_h - 1;
+                glds4_asm((wave == 0 ? lse_b : del_b) + qq, base + 2 * TILE + wave * 256);
+            }
+        };
+        if (GROUPED && j > 0) __syncthreads();   // the previous head's last tile may have been a ragged one, which has no barrier behind it
+        stage(t0, 0);
+        pin_loaded(kf);
+        pin_loaded(vf);
+        dma_drain();
+        __syncthreads();
 
-    sweep_tiles<CAUSAL>(t0, nt, nfull, stage, [&](auto ragged, int buf, int t) __attribute__((always_inline)) {
-        if constexpr (!CAUSAL) dkv_tile<HD, decltype(ragged)::value>(buf * BUF, lse_a, ad, kf, vf, dk, dv, t * 64, Lq, scale_log2e, half);
-        else if (t < nfull && t * 64 >= k0 + 31) dkv_tile<HD, false>(buf * BUF, lse_a, ad, kf, vf, dk, dv, t * 64, Lq, scale_log2e, half);
-        else if (t * 64 + 63 >= k0) dkv_tile<HD, true, true>(buf * BUF, lse_a, ad, kf, vf, dk, dv, t * 64, Lq, scale_log2e, half, key);
-    });
+        sweep_tiles<CAUSAL>(t0, nt, nfull, stage, [&](auto ragged, int buf, int t) __attribute__((always_inline)) {
+            if constexpr (!CAUSAL) dkv_tile<HD, decltype(ragged)::value>(buf * BUF, lse_a, ad, kf, vf, dk, dv, t * 64, Lq_h, scale_log2e, half);
+            else if (t < nfull && t * 64 >= k0 + 31) dkv_tile<HD, false>(buf * BUF, lse_a, ad, kf, vf, dk, dv, t * 64, Lq_h, scale_log2e, half);
+            else if (t * 64 + 63 >= k0) dkv_tile<HD, true, true>(buf * BUF, lse_a, ad, kf, vf, dk, dv, t * 64, Lq_h, scale_log2e, half, key);
+        });
+    };
+    if constexpr (GROUPED) {
+        for (int j = 0; j < hp.group; ++j) sweep_head(j);
+    } else {
+        sweep_head(0);
+    }
     const AttnGrads g = grad_ptrs<HD, CROSS>(grads, hp);
     store_own<DT>(dk, scale, g.dk, g.dk_rs, key, key < Lk, half);
     store_own<DT>(dv, 1.0f, g.dv, g.dv_rs, key, key < Lk, half);
+}
+template <int HD, bool CAUSAL = false, bool CROSS = false>
+__global__ __launch_bounds__(256, CAUSAL ? 2 : 3) void attn_bwd_dkv_kernel(const AttnOps ops, const bf16_t* __restrict__ dO,
+                                                               const float* __restrict__ lse2, const float* __restrict__ delta,
+                                                               const AttnGrads grads, int H, int nblk, float scale, float scale_log2e,
+                                                               int q_begin) {
+    attn_bwd_dkv_body<HD, CAUSAL, CROSS, false>([&]() __attribute__((always_inline)) { return head_ptrs<HD, CROSS>(ops, H, nblk, q_begin); }, dO, lse2, delta, grads, scale, scale_log2e, q_begin);
+}
+// Two instantiations.  One query head per KV head: the plain sweep at the dense kernels' three waves per SIMD.  Grouped: the head loop keeps
+// the staging offsets and the store addresses alive through a head's ragged last tile, which the dense kernel runs after they are dead; at
+// 168 registers that spills (the build refuses it), so the grouped kernel takes the register budget of two waves per SIMD.
+template <bool GROUPED>
+__global__ __launch_bounds__(256, GROUPED ? 2 : 3) void attn_varlen_bwd_dkv_kernel(const AttnOps ops, const SeqTable tab, const bf16_t* __restrict__ dO,
+                                                                                   const float* __restrict__ lse2, const float* __restrict__ delta,
+                                                                                   const AttnGrads grads, int Hq, int Hkv, int M, float scale,
+                                                                                   float scale_log2e) {
+    attn_bwd_dkv_body<64, false, true, GROUPED>([&]() __attribute__((always_inline)) { return varlen_head_ptrs<64, true>(ops, tab, Hq, Hkv, M); }, dO, lse2,
+                                                delta, grads, scale, scale_log2e, 0);
 }
 
 // dQ rows of the queries before q_begin: they received no gradient (the dQ kernel only visits the kept queries)
@@ -690,6 +808,81 @@ extern "C" int vt_attention_cross_bwd(const void* q, int64_t q_rs, const void* k
     const AttnOps ops{(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, q_rs, k_rs, v_rs, Lq, Lk};
     const AttnGrads grads{(bf16_t*)dq, (bf16_t*)dk, (bf16_t*)dv, dq_rs, dk_rs, dv_rs};
     launch_bwd<64, false, true>(ops, o, dO, lse2, B, H, 0, grads, delta_ws, (hipStream_t)stream);
+    VT_CHECK_LAUNCH(who);
+    return VT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// packed variable-length attention with grouped KV heads (the Attn layer of models/model_titok/base/transformer.py:32-62:
+// flash_attn_varlen_func(q, k, v, cu_seqlens, ...) with Hq query heads over Hkv KV heads); head_dim 64, no mask
+// ------------------------------------------------------------------------------------------------
+// Everything about the boundaries is checked here, on the host array, and the table travels in the kernel arguments.
+static int varlen_table(const char* who, const int32_t* cu, int n_seq, int M, int Hq, int Hkv, int hd, SeqTable* tab) {
+    VT_CHECK_ARG(hd == 64, "%s: head_dim %d unsupported (64)", who, hd);
+    VT_CHECK_ARG(M > 0 && Hq > 0 && Hkv > 0, "%s: bad shape M=%d Hq=%d Hkv=%d", who, M, Hq, Hkv);
+    VT_CHECK_ARG(Hq % Hkv == 0, "%s: Hq=%d is not a multiple of Hkv=%d", who, Hq, Hkv);
+    VT_CHECK_ARG(cu != nullptr, "%s: cu_seqlens_host is null", who);
+    VT_CHECK_ARG(n_seq >= 1 && n_seq <= VT_VARLEN_MAX_SEQ, "%s: n_seq=%d outside 1..%d sequences per launch", who, n_seq, VT_VARLEN_MAX_SEQ);
+    VT_CHECK_ARG(cu[0] == 0, "%s: cu_seqlens[0]=%d must be 0", who, cu[0]);
+    for (int b = 0; b < n_seq; ++b)
+        VT_CHECK_ARG(cu[b + 1] > cu[b], "%s: cu_seqlens must increase strictly (no empty sequence): cu[%d]=%d, cu[%d]=%d", who, b, cu[b], b + 1, cu[b + 1]);
+    VT_CHECK_ARG(cu[n_seq] == M, "%s: cu_seqlens[%d]=%d must equal M=%d", who, n_seq, cu[n_seq], M);
+    tab->n = n_seq;
+    int blocks = 0;
+    for (int b = 0; b <= n_seq; ++b) {
+        tab->cu[b] = cu[b];
+        tab->blk[b] = blocks;
+        if (b < n_seq) blocks += (cu[b + 1] - cu[b] + 127) / 128;
+    }
+    for (int b = n_seq + 1; b <= VT_VARLEN_MAX_SEQ; ++b) tab->cu[b] = M, tab->blk[b] = blocks;
+    tab->total = blocks;
+    VT_CHECK_ARG((int64_t)blocks * Hq <= 0x7fffffff, "%s: too many workgroups", who);
+    return VT_OK;
+}
+
+extern "C" int vt_attention_varlen_fwd(const void* q, int64_t q_rs, const void* k, int64_t k_rs, const void* v, int64_t v_rs,
+                                       const int32_t* cu_seqlens_host, int32_t n_seq, int32_t M, int32_t Hq, int32_t Hkv, int32_t hd, void* o,
+                                       float* lse2, vtStream stream) {
+    const char* who = "vt_attention_varlen_fwd";
+    VT_CHECK_ARG(q && k && v && o && lse2, "%s: null pointer", who);
+    SeqTable tab;
+    TRY(varlen_table(who, cu_seqlens_host, n_seq, M, Hq, Hkv, hd, &tab));
+    TRY(cross_stride_check(who, "q", q_rs, Hq));
+    TRY(cross_stride_check(who, "k", k_rs, Hkv));
+    TRY(cross_stride_check(who, "v", v_rs, Hkv));
+    VT_CHECK_ARG(attn_aligned(q, k, v, o), "%s: q, k, v and o must be 16-byte aligned", who);
+    const AttnOps ops{(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, q_rs, k_rs, v_rs, 0, 0};
+    hipLaunchKernelGGL(attn_varlen_fwd_kernel, dim3(tab.total * Hq), dim3(256), 4 * AG<64>::TILE, (hipStream_t)stream, ops, tab, (bf16_t*)o, lse2, Hq,
+                       Hkv, M, kScaleLog2e<64>);
+    VT_CHECK_LAUNCH(who);
+    return VT_OK;
+}
+
+extern "C" int vt_attention_varlen_bwd(const void* q, int64_t q_rs, const void* k, int64_t k_rs, const void* v, int64_t v_rs, const void* o,
+                                       const void* dO, const float* lse2, const int32_t* cu_seqlens_host, int32_t n_seq, int32_t M, int32_t Hq,
+                                       int32_t Hkv, int32_t hd, void* dq, int64_t dq_rs, void* dk, int64_t dk_rs, void* dv, int64_t dv_rs,
+                                       float* delta_ws, vtStream stream) {
+    const char* who = "vt_attention_varlen_bwd";
+    VT_CHECK_ARG(q && k && v && o && dO && lse2 && dq && dk && dv && delta_ws, "%s: null pointer", who);
+    SeqTable tab;
+    TRY(varlen_table(who, cu_seqlens_host, n_seq, M, Hq, Hkv, hd, &tab));
+    TRY(cross_stride_check(who, "q", q_rs, Hq));
+    TRY(cross_stride_check(who, "k", k_rs, Hkv));
+    TRY(cross_stride_check(who, "v", v_rs, Hkv));
+    TRY(cross_stride_check(who, "dq", dq_rs, Hq));
+    TRY(cross_stride_check(who, "dk", dk_rs, Hkv));
+    TRY(cross_stride_check(who, "dv", dv_rs, Hkv));
+    VT_CHECK_ARG(attn_aligned(q, k, v, o) && attn_aligned(dO, dq, dk, dv), "%s: q, k, v, o, dO, dq, dk and dv must be 16-byte aligned", who);
+    const AttnOps ops{(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, q_rs, k_rs, v_rs, 0, 0};
+    const AttnGrads grads{(bf16_t*)dq, (bf16_t*)dk, (bf16_t*)dv, dq_rs, dk_rs, dv_rs};
+    hipLaunchKernelGGL(attn_varlen_bwd_dq_kernel, dim3(tab.total * Hq), dim3(256), 4 * AG<64>::TILE, (hipStream_t)stream, ops, tab, (const bf16_t*)o,
+                       (const bf16_t*)dO, lse2, delta_ws, grads, Hq, Hkv, M, kScale<64>, kScaleLog2e<64>);
+    if (Hq == Hkv)
+        hipLaunchKernelGGL(attn_varlen_bwd_dkv_kernel<false>, dim3(tab.total * Hkv), dim3(256), 2 * (2 * AG<64>::TILE + 512), (hipStream_t)stream, ops,
+                           tab, (const bf16_t*)dO, lse2, delta_ws, grads, Hq, Hkv, M, kScale<64>, kScaleLog2e<64>);
+    else
+        hipLaunchKernelGGL(attn_varlen_bwd_dkv_kernel<true>, dim3(tab.total * Hkv), dim3(256), 2 * (2 * AG<64>::TILE + 512), (hipStream_t)stream, ops,
+                           tab, (const bf16_t*)dO, lse2, delta_ws, grads, Hq, Hkv, M, kScale<64>, kScaleLog2e<64>);
     VT_CHECK_LAUNCH(who);
     return VT_OK;
 }

@@ -14,125 +14,10 @@
 // every product are rounded to bf16 where the reference materialises a bf16 tensor; statistics and products are fp32.
 #include "vt_common.h"
 #include "vt_headvec.h"
+#include "vt_qknorm.h"
 
 namespace {
-constexpr int NBLK = 512;    // blocks per operand in the backward (partial sums: [NBLK, 2, 2, 64] fp32)
-
-// LayerNorm statistics of one 64-vector spread over 8 lanes (biased variance, two passes in registers)
-__device__ __forceinline__ void ln_stats(const Vec8& x, float eps, float& mean, float& rstd) {
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) s += x.v[i];
-    mean = sum8(s) * (1.0f / HD);
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) q += (x.v[i] - mean) * (x.v[i] - mean);
-    rstd = 1.0f / sqrtf(sum8(q) * (1.0f / HD) + eps);
-}
-
-// grid (blocks, 3): y = 0 -> q, 1 -> k, 2 -> v (copy)
-__global__ __launch_bounds__(256) void qknorm_rope_fwd_kernel(const bf16_t* __restrict__ qkvg, int64_t M, int L, int H, const float* __restrict__ q_w,
-                                                               const float* __restrict__ q_b, const float* __restrict__ k_w,
-                                                               const float* __restrict__ k_b, float eps, const float* __restrict__ cs,
-                                                               const float* __restrict__ sn, bf16_t* __restrict__ out) {
-    const int which = blockIdx.y, lane = threadIdx.x & 7;
-    const int64_t D = (int64_t)H * HD, nvec = M * H;
-    const float* w = which == 0 ? q_w : k_w;
-    const float* b = which == 0 ? q_b : k_b;
-    float wr[8], br[8];
-    if (which < 2) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) wr[i] = w[lane * 8 + i], br[i] = b[lane * 8 + i];
-    }
-    for (int64_t vec = (int64_t)blockIdx.x * VPB + (threadIdx.x >> 3); vec < nvec; vec += (int64_t)gridDim.x * VPB) {
-        const int64_t row = vec / H;
-        const int head = (int)(vec % H);
-        const bf16_t* src = qkvg + row * 4 * D + which * D + head * HD + lane * 8;
-        bf16_t* dst = out + row * 3 * D + which * D + head * HD + lane * 8;
-        if (which == 2) {
-            *(bf16x8*)dst = *(const bf16x8*)src;
-            continue;
-        }
-        Vec8 x = load8(src);
-        float mean, rstd;
-        ln_stats(x, eps, mean, rstd);
-        const int pos = (int)(row % L);
-        const f32x4 c = *(const f32x4*)(cs + (int64_t)pos * (HD / 2) + lane * 4);
-        const f32x4 s = *(const f32x4*)(sn + (int64_t)pos * (HD / 2) + lane * 4);
-        Vec8 y;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float a = round_bf16((x.v[2 * j] - mean) * rstd * wr[2 * j] + br[2 * j]);
-            const float bb = round_bf16((x.v[2 * j + 1] - mean) * rstd * wr[2 * j + 1] + br[2 * j + 1]);
-            y.v[2 * j] = a * c[j] - bb * s[j];
-            y.v[2 * j + 1] = a * s[j] + bb * c[j];
-        }
-        store8(dst, y);
-    }
-}
-
-// grid (NBLK, 3).  part: [NBLK, 2(which), 2(w|b), 64]
-__global__ __launch_bounds__(256) void qknorm_rope_bwd_kernel(const bf16_t* __restrict__ qkvg, const bf16_t* __restrict__ dqkv, int64_t M, int L, int H,
-                                                               const float* __restrict__ q_w, const float* __restrict__ k_w, float eps,
-                                                               const float* __restrict__ cs, const float* __restrict__ sn,
-                                                               bf16_t* __restrict__ dqkvg, float* __restrict__ part) {
-    __shared__ float red[2][VPB][HD];
-    const int which = blockIdx.y, lane = threadIdx.x & 7, vslot = threadIdx.x >> 3;
-    const int64_t D = (int64_t)H * HD, nvec = M * H;
-    float wr[8], aw[8], ab[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) aw[i] = 0.f, ab[i] = 0.f, wr[i] = which < 2 ? (which == 0 ? q_w : k_w)[lane * 8 + i] : 0.f;
-    for (int64_t vec = (int64_t)blockIdx.x * VPB + vslot; vec < nvec; vec += (int64_t)gridDim.x * VPB) {
-        const int64_t row = vec / H;
-        const int head = (int)(vec % H);
-        const bf16_t* gsrc = dqkv + row * 3 * D + which * D + head * HD + lane * 8;
-        bf16_t* dst = dqkvg + row * 4 * D + which * D + head * HD + lane * 8;
-        if (which == 2) {
-            *(bf16x8*)dst = *(const bf16x8*)gsrc;
-            continue;
-        }
-        const Vec8 x = load8(qkvg + row * 4 * D + which * D + head * HD + lane * 8);
-        const Vec8 gy = load8(gsrc);
-        float mean, rstd;
-        ln_stats(x, eps, mean, rstd);
-        const int pos = (int)(row % L);
-        const f32x4 c = *(const f32x4*)(cs + (int64_t)pos * (HD / 2) + lane * 4);
-        const f32x4 s = *(const f32x4*)(sn + (int64_t)pos * (HD / 2) + lane * 4);
-        // transpose of the rotation, rounded to bf16 (the gradient of a bf16 tensor), then LayerNorm backward in fp32
-        float g[8], xh[8], m1 = 0.f, m2 = 0.f;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            g[2 * j] = round_bf16(gy.v[2 * j] * c[j] + gy.v[2 * j + 1] * s[j]);
-            g[2 * j + 1] = round_bf16(gy.v[2 * j + 1] * c[j] - gy.v[2 * j] * s[j]);
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            xh[i] = (x.v[i] - mean) * rstd;
-            aw[i] += g[i] * xh[i];
-            ab[i] += g[i];
-            m1 += g[i] * wr[i];
-            m2 += g[i] * wr[i] * xh[i];
-        }
-        m1 = sum8(m1) * (1.0f / HD);
-        m2 = sum8(m2) * (1.0f / HD);
-        Vec8 dx;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) dx.v[i] = rstd * (g[i] * wr[i] - m1 - xh[i] * m2);
-        store8(dst, dx);
-    }
-    if (which == 2) return;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) red[0][vslot][lane * 8 + i] = aw[i], red[1][vslot][lane * 8 + i] = ab[i];
-    __syncthreads();
-    if (threadIdx.x < 2 * HD) {
-        const int wb = threadIdx.x >> 6, e = threadIdx.x & 63;
-        float t = 0.f;
-#pragma unroll 8
-        for (int v = 0; v < VPB; ++v) t += red[wb][v][e];
-        part[(((int64_t)blockIdx.x * 2 + which) * 2 + wb) * HD + e] = t;
-    }
-}
-
+// (the q/k LayerNorm + rotary kernels are in vt_qknorm.h, shared with the grouped pass of vt_varlen.hip)
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + __expf(-x)); }
 
 // gate: first gate column of row 0, gate_rs its row stride (the block's gate is qkvg + 3D with stride 4D; vt_sigmoid_gate_cols_* takes any)
@@ -212,15 +97,14 @@ extern "C" int vt_qknorm_rope_fwd(const void* qkvg, int64_t M, int32_t L, int32_
     VT_CHECK_ARG(qkvg && qkv_out && q_w && q_b && k_w && k_b && cos_tab && sin_tab, "vt_qknorm_rope_fwd: null pointer");
     VT_CHECK_ARG(M > 0 && L > 0 && H > 0 && M % L == 0, "vt_qknorm_rope_fwd: need M = B * L rows, H heads of 64");
     VT_CHECK_ARG(aligned16(qkvg) && aligned16(qkv_out) && aligned16(cos_tab) && aligned16(sin_tab), "vt_qknorm_rope_fwd: buffers must be 16-byte aligned");
-    const int64_t nvec = M * H;
-    const int gx = (int)((nvec + VPB - 1) / VPB < 2048 ? (nvec + VPB - 1) / VPB : 2048);
-    hipLaunchKernelGGL(qknorm_rope_fwd_kernel, dim3(gx, 3), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)qkvg, M, L, H, q_w, q_b, k_w, k_b, eps,
-                       cos_tab, sin_tab, (bf16_t*)qkv_out);
+    const int64_t D = (int64_t)H * HD;
+    hipLaunchKernelGGL(qknorm_rope_fwd_kernel, dim3(qkn_fwd_grid(M, H), 3), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)qkvg, 4 * D, M, (int64_t)L,
+                       H, H, q_w, q_b, k_w, k_b, eps, cos_tab, sin_tab, (bf16_t*)qkv_out, 3 * D);
     VT_CHECK_LAUNCH("vt_qknorm_rope_fwd");
     return VT_OK;
 }
 
-extern "C" size_t vt_qknorm_rope_bwd_workspace_bytes(void) { return (size_t)NBLK * 256 * sizeof(float); }
+extern "C" size_t vt_qknorm_rope_bwd_workspace_bytes(void) { return (size_t)QKN_NBLK * 256 * sizeof(float); }
 
 extern "C" int vt_qknorm_rope_bwd(const void* qkvg, const void* dqkv, int64_t M, int32_t L, int32_t H, const float* q_w, const float* k_w, float eps,
                                   const float* cos_tab, const float* sin_tab, void* dqkvg, float* dq_w, float* dq_b, float* dk_w, float* dk_b,
@@ -229,10 +113,11 @@ extern "C" int vt_qknorm_rope_bwd(const void* qkvg, const void* dqkv, int64_t M,
     VT_CHECK_ARG(M > 0 && L > 0 && H > 0 && M % L == 0, "vt_qknorm_rope_bwd: need M = B * L rows, H heads of 64");
     VT_CHECK_ARG(aligned16(qkvg) && aligned16(dqkv) && aligned16(dqkvg) && aligned16(cos_tab) && aligned16(sin_tab) && aligned16(workspace),
                  "vt_qknorm_rope_bwd: buffers must be 16-byte aligned");
-    hipLaunchKernelGGL(qknorm_rope_bwd_kernel, dim3(NBLK, 3), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)qkvg, (const bf16_t*)dqkv, M, L, H, q_w, k_w,
-                       eps, cos_tab, sin_tab, (bf16_t*)dqkvg, (float*)workspace);
+    const int64_t D = (int64_t)H * HD;
+    hipLaunchKernelGGL(qknorm_rope_bwd_kernel, dim3(QKN_NBLK, 3), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)qkvg, 4 * D, (const bf16_t*)dqkv, 3 * D, M,
+                       (int64_t)L, H, H, q_w, k_w, eps, cos_tab, sin_tab, (bf16_t*)dqkvg, 4 * D, (float*)workspace);
     VT_CHECK_LAUNCH("vt_qknorm_rope_bwd");
-    return vt_reduce_waves("vt_qknorm_rope_bwd(reduce)", (const float*)workspace, NBLK, 4 * HD, 4 * HD, dq_w, dq_b, dk_w, dk_b, stream);
+    return vt_reduce_waves("vt_qknorm_rope_bwd(reduce)", (const float*)workspace, QKN_NBLK, 4 * HD, 4 * HD, dq_w, dq_b, dk_w, dk_b, stream);
 }
 
 // `who`: the entry point's name, so that a refusal or a launch failure is reported under the caller's own name

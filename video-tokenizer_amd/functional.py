@@ -719,3 +719,84 @@ class FeedForwardLayer(torch.autograd.Function):
             dw2 = dw2p[:, :inner].contiguous()
         dx, _, dn_w = hip.rmsnorm_any_bwd(dxn, x2, n_w, rstd, dres=d2)
         return dx.reshape(dout.shape) if need[0] else None, ds, dn_w if need[2] else None, dw1, dw2, None, None, None
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# packed variable-length attention with grouped KV heads and model_titok's Attn layer (models/model_titok/base/transformer.py:32-62)
+# ------------------------------------------------------------------------------------------------------------------------
+class VarlenAttend(torch.autograd.Function):
+    """flash_attn_varlen_func(q, k, v, cu_seqlens, cu_seqlens, ...) on vt_attention_varlen_*: head_dim 64, no mask, scale 1/8.  q a bf16 view
+    [M, 64 Hq], k and v bf16 views [M, 64 Hkv] with a row stride each (the column blocks of one projection are read in place), sequence b =
+    rows cu_seqlens[b] .. cu_seqlens[b+1]-1, query head h on KV head h // (Hq // Hkv) -> o bf16 [M, 64 Hq].  cu_seqlens: a list, or a CPU or
+    device int tensor (a device tensor costs one synchronisation per call, forward and backward share the read)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, cu_seqlens, Hq, Hkv):
+        cu = hip.cu_seqlens_list(cu_seqlens)                             # the one conversion: backward reuses the list
+        o, lse2 = hip.attention_varlen_fwd(q, k, v, cu, Hq, Hkv)
+        ctx.save_for_backward(q, k, v, o, lse2)
+        ctx.geom = (cu, Hq, Hkv)
+        return o
+
+    @staticmethod
+    def backward(ctx, dO):
+        q, k, v, o, lse2 = ctx.saved_tensors
+        dq, dk, dv = hip.attention_varlen_bwd(q, k, v, o, dO.contiguous().to(torch.bfloat16), lse2, *ctx.geom)
+        return dq, dk, dv, None, None, None
+
+
+class VarlenAttentionLayer(torch.autograd.Function):
+    """Attn.forward (models/model_titok/base/transformer.py:46-62) on a packed batch x fp32 [M, D], D = 64 Hq, as five launches: LayerNorm(x);
+    the to_qkv GEMM (N = D + 128 Hkv, columns q | k | v); vt_qknorm_rope_gqa_fwd (per-head LayerNorm and rotation of q and k by table row m, v
+    copied); vt_attention_varlen_fwd on the three column blocks in place; out_proj.  Rounding points of autocast(bf16): bf16 Linear outputs,
+    bf16 head norm and rotation, bf16 attention output, fp32 x and dx.  cos / sin: fp32 [M, 32] device tables (varlen.rope_freqs); cu: the
+    sequence boundaries as a host list.  pk_*: (bf16 [N, K], bf16 [K, N]) operand copies of to_qkv and out_proj (packs.get)."""
+
+    @staticmethod
+    def forward(ctx, x, cos, sin, cu, pre_w, pre_b, to_qkv_w, q_w, q_b, k_w, k_b, out_proj_w, Hq, Hkv, eps, pk_qkv, pk_o):
+        hip.require_gpu(x, cos, sin, pre_w, pre_b, to_qkv_w, q_w, q_b, k_w, k_b, out_proj_w)
+        M, D = x.shape
+        G = 64 * Hkv
+        assert D == 64 * Hq and to_qkv_w.shape == (D + 2 * G, D) and cos.shape == (M, 32) == sin.shape
+        x2 = x.contiguous().float()
+        pw, pb, qw, qb, kw, kb = (t.detach().float().contiguous() for t in (pre_w, pre_b, q_w, q_b, k_w, k_b))
+        cos, sin = cos.contiguous(), sin.contiguous()
+        xn, mean, rstd = hip.layernorm_fwd(x2, pw, pb, eps)
+        qkv = hip.gemm_nt(xn, pk_qkv[0], hip.EPI_BF16)                   # [M, D + 2G] = [q | k | v]
+        qkr = hip.qknorm_rope_gqa_fwd(qkv, Hq, Hkv, qw, qb, kw, kb, eps, cos, sin)
+        o, lse2 = hip.attention_varlen_fwd(qkr[:, :D], qkr[:, D:D + G], qkr[:, D + G:], cu, Hq, Hkv)
+        out = hip.gemm_nt(o, pk_o[0], hip.EPI_F32, round_bf16=True)
+        ctx.save_for_backward(x2, pw, qw, kw, cos, sin, mean, rstd, xn, qkv, qkr, o, lse2, pk_qkv[1], pk_o[1])
+        ctx.geom = (list(cu), Hq, Hkv, eps)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x2, pw, qw, kw, cos, sin, mean, rstd, xn, qkv, qkr, o, lse2, wqkv_t, wo_t = ctx.saved_tensors
+        cu, Hq, Hkv, eps = ctx.geom
+        M, D = x2.shape
+        G = 64 * Hkv
+        dev = dout.device
+        need = ctx.needs_input_grad
+        gb = hip.cast_rows(dout.contiguous().float())
+        d_o = hip.gemm_nt(gb, wo_t, hip.EPI_BF16)
+        dqkr = torch.empty(M, D + 2 * G, device=dev, dtype=torch.bfloat16)  # gradient of the rotated [q | k | v], every column written below
+        hip.attention_varlen_bwd(qkr[:, :D], qkr[:, D:D + G], qkr[:, D + G:], o, d_o, lse2, cu, Hq, Hkv, dq=dqkr[:, :D], dk=dqkr[:, D:D + G],
+                                 dv=dqkr[:, D + G:])
+        dqkv, (dq_w, dq_b, dk_w, dk_b) = hip.qknorm_rope_gqa_bwd(qkv, dqkr, Hq, Hkv, qw, kw, eps, cos, sin)
+        dxn = hip.gemm_nt(dqkv, wqkv_t, hip.EPI_BF16)
+        dwqkv = dwo = None
+        jobs = []
+        if need[6]:
+            dwqkv = torch.empty(D + 2 * G, D, device=dev)
+            a_, b_ = _rows64(dqkv, xn)
+            jobs.append(dict(A=a_, B=b_, out=dwqkv))
+        if need[11]:
+            dwo = torch.empty(D, D, device=dev)
+            a_, b_ = _rows64(gb, o)
+            jobs.append(dict(A=a_, B=b_, out=dwo))
+        if jobs:
+            hip.gemm_tn_grouped(jobs)
+        dx, _, dg, db, _ = hip.layernorm_bwd(dxn, x2, pw, mean, rstd, want_dxsum=False, want_dxb=False)
+        return (dx if need[0] else None, None, None, None, dg if need[4] else None, db if need[5] else None, dwqkv, dq_w if need[7] else None,
+                dq_b if need[8] else None, dk_w if need[9] else None, dk_b if need[10] else None, dwo, None, None, None, None, None)

@@ -70,6 +70,10 @@ SIGNATURES = {
     "vt_attention_cross_fwd": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "vt_attention_cross_bwd": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i64,
                                        c_vp, c_i64, c_vp, c_i64, c_vp, c_vp]),
+    "vt_attention_varlen_fwd": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, ctypes.POINTER(c_i32), c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp,
+                                        c_vp]),
+    "vt_attention_varlen_bwd": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, ctypes.POINTER(c_i32), c_i32, c_i32, c_i32, c_i32,
+                                        c_i32, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp]),
     "vt_vq_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32]),
     "vt_vq_forward": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_f32, c_f32, c_f32, c_u64, c_vp, c_vp,
                               c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
@@ -94,6 +98,10 @@ SIGNATURES = {
     "vt_qknorm_rope_fwd": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp]),
     "vt_qknorm_rope_bwd_workspace_bytes": (c_sz, []),
     "vt_qknorm_rope_bwd": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "vt_qknorm_rope_gqa_fwd": (c_i32, [c_vp, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "vt_qknorm_rope_gqa_bwd_workspace_bytes": (c_sz, []),
+    "vt_qknorm_rope_gqa_bwd": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp,
+                                       c_vp, c_vp]),
     "vt_rope_rotate": (c_i32, [c_vp, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp]),
     "vt_sigmoid_gate_fwd": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_vp]),
     "vt_sigmoid_gate_bwd": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp]),
@@ -518,6 +526,103 @@ def attention_cross_bwd(q, k, v, o, dO, lse2, B, Lq, Lk, H, hd=64, dq=None, dk=N
                                        B, Lq, Lk, H, hd, ptr(dq), _rows_view(dq, "dq"), ptr(dk), _rows_view(dk, "dk"), ptr(dv), _rows_view(dv, "dv"),
                                        ptr(delta), stream()), "vt_attention_cross_bwd")
     return dq, dk, dv
+
+
+VARLEN_MAX_SEQ = 64      # VT_VARLEN_MAX_SEQ
+
+
+def cu_seqlens_list(cu_seqlens):
+    """sequence boundaries as a list of Python ints: from a list / tuple of ints, or a CPU or device int32 / int64 tensor.  THE conversion
+    of the package (VarlenAttend, varlen.Attn and cu_seqlens_host all go through it), so a float tensor or a float in a list is refused
+    here and nowhere truncated.  A DEVICE tensor is read back, which costs one synchronisation: build the list on the host where that matters."""
+    if isinstance(cu_seqlens, torch.Tensor):
+        if cu_seqlens.dim() != 1 or cu_seqlens.dtype not in (torch.int32, torch.int64):
+            raise HipError(f"cu_seqlens: expected a 1-D int32 / int64 tensor, got {cu_seqlens.dtype} {tuple(cu_seqlens.shape)}")
+        cu_seqlens = cu_seqlens.tolist()
+    cu = []
+    for c in cu_seqlens:
+        if isinstance(c, bool) or int(c) != c or isinstance(c, float):
+            raise HipError(f"cu_seqlens: boundaries must be integers, got {c!r}")
+        cu.append(int(c))
+    if len(cu) < 2:
+        raise HipError("cu_seqlens: need at least one sequence (two boundaries)")
+    if any(not -2**31 <= c < 2**31 for c in cu):
+        raise HipError("cu_seqlens: a boundary does not fit int32")
+    return cu
+
+
+def cu_seqlens_host(cu_seqlens):
+    """-> (the host int32 array the C ABI takes, n_seq, M).  The library validates the values (cu[0] == 0, strictly increasing, cu[n] == M, at
+    most VARLEN_MAX_SEQ sequences)."""
+    cu = cu_seqlens_list(cu_seqlens)
+    return (c_i32 * len(cu))(*cu), len(cu) - 1, cu[-1]
+
+
+def attention_varlen_fwd(q, k, v, cu_seqlens, Hq, Hkv, hd=64, o=None, lse2=None):
+    """softmax(q k^T / 8) v inside every sequence of a packed batch: q a view [M, 64 Hq], k and v views [M, 64 Hkv] of wider bf16 buffers,
+    sequence b = rows cu_seqlens[b] .. cu_seqlens[b+1]-1, query head h reads KV head h // (Hq // Hkv) -> (o bf16 [M, 64 Hq], lse2 fp32 [Hq, M])"""
+    require_gpu(q, k, v)
+    cu, n, _ = cu_seqlens_host(cu_seqlens)
+    M = q.shape[0]
+    assert tuple(q.shape) == (M, Hq * hd) and tuple(k.shape) == (M, Hkv * hd) == tuple(v.shape)
+    o = torch.empty(M, Hq * hd, device=q.device, dtype=torch.bfloat16) if o is None else o
+    lse2 = torch.empty(Hq, M, device=q.device, dtype=torch.float32) if lse2 is None else lse2
+    assert o.is_contiguous() and tuple(o.shape) == (M, Hq * hd) and lse2.is_contiguous() and tuple(lse2.shape) == (Hq, M)
+    check(lib().vt_attention_varlen_fwd(ptr(q), _rows_view(q, "q"), ptr(k), _rows_view(k, "k"), ptr(v), _rows_view(v, "v"), cu, n, M, Hq, Hkv, hd,
+                                        ptr(o), ptr(lse2), stream()), "vt_attention_varlen_fwd")
+    return o, lse2
+
+
+def attention_varlen_bwd(q, k, v, o, dO, lse2, cu_seqlens, Hq, Hkv, hd=64, dq=None, dk=None, dv=None):
+    """-> (dq [M, 64 Hq], dk, dv [M, 64 Hkv]); each may be passed as a view of a wider bf16 buffer, whose other columns are left alone"""
+    require_gpu(q, k, v, o, dO, lse2, dq, dk, dv)
+    cu, n, _ = cu_seqlens_host(cu_seqlens)
+    M = q.shape[0]
+    assert tuple(q.shape) == (M, Hq * hd) and tuple(k.shape) == (M, Hkv * hd) == tuple(v.shape)
+    assert o.is_contiguous() and dO.is_contiguous() and tuple(o.shape) == (M, Hq * hd) == tuple(dO.shape)
+    assert lse2.is_contiguous() and tuple(lse2.shape) == (Hq, M) and lse2.dtype == torch.float32
+    dq = torch.empty(M, Hq * hd, device=q.device, dtype=torch.bfloat16) if dq is None else dq
+    dk = torch.empty(M, Hkv * hd, device=q.device, dtype=torch.bfloat16) if dk is None else dk
+    dv = torch.empty(M, Hkv * hd, device=q.device, dtype=torch.bfloat16) if dv is None else dv
+    assert tuple(dq.shape) == (M, Hq * hd) and tuple(dk.shape) == (M, Hkv * hd) == tuple(dv.shape)
+    delta = torch.empty(Hq, M, device=q.device, dtype=torch.float32)
+    check(lib().vt_attention_varlen_bwd(ptr(q), _rows_view(q, "q"), ptr(k), _rows_view(k, "k"), ptr(v), _rows_view(v, "v"), ptr(o), ptr(dO), ptr(lse2),
+                                        cu, n, M, Hq, Hkv, hd, ptr(dq), _rows_view(dq, "dq"), ptr(dk), _rows_view(dk, "dk"), ptr(dv),
+                                        _rows_view(dv, "dv"), ptr(delta), stream()), "vt_attention_varlen_bwd")
+    return dq, dk, dv
+
+
+def _gqa_tables_ok(cos, sin, M):
+    return (tuple(cos.shape) == (M, 32) == tuple(sin.shape) and cos.dtype == torch.float32 == sin.dtype and cos.is_contiguous()
+            and sin.is_contiguous())
+
+
+def qknorm_rope_gqa_fwd(qkv, Hq, Hkv, q_w, q_b, k_w, k_b, eps, cos, sin, out=None):
+    """qkv: a bf16 view [M, 64 (Hq + 2 Hkv)] (columns q | k | v) -> the same layout with q and k LayerNorm_64'd and rotated by table row m
+    (cos / sin fp32 [M, 32]), v copied"""
+    require_gpu(qkv, q_w, q_b, k_w, k_b, cos, sin, out)
+    M, W = qkv.shape
+    assert W == 64 * (Hq + 2 * Hkv) and _gqa_tables_ok(cos, sin, M)
+    out = torch.empty(M, W, device=qkv.device, dtype=torch.bfloat16) if out is None else out
+    assert tuple(out.shape) == (M, W)
+    check(lib().vt_qknorm_rope_gqa_fwd(ptr(qkv), _rows_view(qkv, "qkv"), M, Hq, Hkv, ptr(q_w), ptr(q_b), ptr(k_w), ptr(k_b), eps, ptr(cos), ptr(sin),
+                                       ptr(out), _rows_view(out, "out"), stream()), "vt_qknorm_rope_gqa_fwd")
+    return out
+
+
+def qknorm_rope_gqa_bwd(qkv, dout, Hq, Hkv, q_w, k_w, eps, cos, sin, dqkv=None):
+    """dout: gradient of qknorm_rope_gqa_fwd's output -> (dqkv, [dq_w, dq_b, dk_w, dk_b] fp32 [64] each)"""
+    require_gpu(qkv, dout, q_w, k_w, cos, sin, dqkv)
+    M, W = qkv.shape
+    assert W == 64 * (Hq + 2 * Hkv) and tuple(dout.shape) == (M, W) and _gqa_tables_ok(cos, sin, M)
+    dqkv = torch.empty(M, W, device=qkv.device, dtype=torch.bfloat16) if dqkv is None else dqkv
+    assert tuple(dqkv.shape) == (M, W)
+    grads = [torch.empty(64, device=qkv.device, dtype=torch.float32) for _ in range(4)]
+    ws = _ws(lib().vt_qknorm_rope_gqa_bwd_workspace_bytes(), qkv.device)
+    check(lib().vt_qknorm_rope_gqa_bwd(ptr(qkv), _rows_view(qkv, "qkv"), ptr(dout), _rows_view(dout, "dout"), M, Hq, Hkv, ptr(q_w), ptr(k_w), eps,
+                                       ptr(cos), ptr(sin), ptr(dqkv), _rows_view(dqkv, "dqkv"), ptr(grads[0]), ptr(grads[1]), ptr(grads[2]),
+                                       ptr(grads[3]), ptr(ws), stream()), "vt_qknorm_rope_gqa_bwd")
+    return dqkv, grads
 
 
 def head_rmsnorm_fwd(x, w, eps, H):
