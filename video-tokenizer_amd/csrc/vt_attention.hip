@@ -34,6 +34,8 @@
 #include "vt_common.h"
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "vt_attn_tile.h"
 
 namespace {
@@ -41,6 +43,8 @@ namespace {
 // One workgroup's (batch, head, row-block) and the first Q / K / V row of that head.  1-D grid, XCD-aware: the nblk row-blocks of one
 // (batch, head) get consecutive ids inside ONE XCD's chunk, so the tiles they all stream (K/V in fwd and dQ, Q/dO in dK/dV) are
 // fetched into that XCD's L2 once instead of once per XCD.  Returned BY VALUE: the fields are scalars the kernels keep in SGPRs.
+// (id, count): the workgroup's index among the `count` workgroups that share its mapping -- blockIdx.x of gridDim.x in a launch of one
+// kind of workgroup, the index within its role in the two-role backward launch (attn_bwd_kernel).
 // The operands of a launch (kernel arguments).  Packed: q = qkv [B, L, 3, H, HD] and Lq = L are read, the other fields are not.
 struct AttnOps {
     const bf16_t *q, *k, *v;
@@ -64,9 +68,9 @@ struct HeadPtrs {
     const bf16_t *qb, *kb, *vb;
 };
 template <int HD, bool CROSS>
-__device__ __forceinline__ HeadPtrs head_ptrs(const AttnOps& a, int H, int nblk, int q_begin) {
+__device__ __forceinline__ HeadPtrs head_ptrs(const AttnOps& a, int H, int nblk, int q_begin, int id, int count) {
     HeadPtrs p;
-    const int sid = xcd_remap(blockIdx.x, gridDim.x);
+    const int sid = xcd_remap(id, count);
     const int bh = sid / nblk;
     p.blk = sid - bh * nblk;
     const int b = bh / H, h = bh % H;
@@ -342,7 +346,7 @@ __device__ __forceinline__ void attn_fwd_body(Heads&& heads, bf16_t* __restrict_
 template <int HD, bool CAUSAL = false, bool CROSS = false>
 __global__ __launch_bounds__(256, CAUSAL ? 3 : 4) void attn_fwd_kernel(const AttnOps ops, bf16_t* __restrict__ o, float* __restrict__ lse2,
                                                            int H, int nblk, float scale_log2e, int q_begin) {
-    attn_fwd_body<HD, CAUSAL, CROSS>([&]() __attribute__((always_inline)) { return head_ptrs<HD, CROSS>(ops, H, nblk, q_begin); }, o, lse2, scale_log2e, q_begin);
+    attn_fwd_body<HD, CAUSAL, CROSS>([&]() __attribute__((always_inline)) { return head_ptrs<HD, CROSS>(ops, H, nblk, q_begin, blockIdx.x, gridDim.x); }, o, lse2, scale_log2e, q_begin);
 }
 __global__ __launch_bounds__(256, 4) void attn_varlen_fwd_kernel(const AttnOps ops, const SeqTable tab, bf16_t* __restrict__ o,
                                                                  float* __restrict__ lse2, int Hq, int Hkv, int M, float scale_log2e) {
@@ -385,15 +389,30 @@ __device__ __forceinline__ void dq_tile(unsigned kl, unsigned vl, const TileAddr
     }
 }
 
+// delta[b,h,q] = sum_d dO[b,q,h,d] * O[b,q,h,d] of a lane's own row from its load_own fragments of O and dO.  ONE expression for both of its
+// users (the dQ body and attn_delta_kernel), the 8 * KS products of a lane in this order and then the exchange between the lane halves, so
+// that delta has the same bits whichever of them wrote it.
+template <int KS>
+__device__ __forceinline__ float delta_own(const bf16x8 (&of)[KS], const bf16x8 (&dof)[KS]) {
+    float d = 0.f;
+#pragma unroll
+    for (int s = 0; s < KS; ++s)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) d += bf2f(of[s][j]) * bf2f(dof[s][j]);
+    d += __shfl_xor(d, 32);   // the two lane halves hold the two halves of every 16-wide k-step
+    return d;
+}
+
 // ------------------------------------------------------------------------------------------------
-// dQ: own rows = queries; streams K (row reads + transposed reads) and V (row reads).  Also produces
-// delta[b,h,q] = sum_d dO[b,q,h,d] * O[b,q,h,d] for its own rows (both operands are one 16-B load per k-step away) and
-// leaves it in `delta` for the dK/dV kernel, which is launched behind this one.
+// dQ: own rows = queries; streams K (row reads + transposed reads) and V (row reads).  OWN_DELTA (the causal and the variable-length
+// launches): also produces delta for its own rows (both operands are one 16-B load per k-step away) and leaves it in `delta` for the
+// dK/dV kernel, which is launched behind this one.  Otherwise (the dQ role of attn_bwd_kernel) `delta` was filled by attn_delta_kernel
+// and is only read here, and `o` is not.
 // ------------------------------------------------------------------------------------------------
-template <int HD, bool CAUSAL, bool CROSS, class Heads>
+template <int HD, bool CAUSAL, bool CROSS, bool OWN_DELTA, class Heads>
 __device__ __forceinline__ void attn_bwd_dq_body(Heads&& heads, const bf16_t* __restrict__ o, const bf16_t* __restrict__ dO,
-                                                 const float* __restrict__ lse2, float* __restrict__ delta, const AttnGrads grads, float scale,
-                                                 float scale_log2e, int q_begin) {
+                                                 const float* __restrict__ lse2, std::conditional_t<OWN_DELTA, float, const float>* __restrict__ delta,
+                                                 const AttnGrads grads, float scale, float scale_log2e, int q_begin) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -410,16 +429,14 @@ __device__ __forceinline__ void attn_bwd_dq_body(Heads&& heads, const bf16_t* __
     load_own<KS>(hp.qb, hp.q_rs, q0, Lq, lane, qf);
     load_own<KS>(dO + hp.orow * hp.ors + (int64_t)hp.hq * HD, hp.ors, q0 - q_begin, Lo, lane, dof);
     const float my_lse = lse2[hp.st_off + qc];
-    float my_delta = 0.f;
-    {
+    float my_delta;
+    if constexpr (OWN_DELTA) {
         bf16x8 of[KS];
         load_own<KS>(o + hp.orow * hp.ors + (int64_t)hp.hq * HD, hp.ors, q0 - q_begin, Lo, lane, of);
-#pragma unroll
-        for (int s = 0; s < KS; ++s)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) my_delta += bf2f(of[s][j]) * bf2f(dof[s][j]);
-        my_delta += __shfl_xor(my_delta, 32);   // the two lane halves hold the two halves of every 16-wide k-step
+        my_delta = delta_own<KS>(of, dof);
         if (q < Lq && half == 0) delta[hp.st_off + q] = my_delta;
+    } else {
+        my_delta = delta[hp.st_off + qc];
     }
 
     f32x16 dq[DT];
@@ -460,18 +477,18 @@ __device__ __forceinline__ void attn_bwd_dq_body(Heads&& heads, const bf16_t* __
     const AttnGrads g = grad_ptrs<HD, CROSS>(grads, hp);
     store_own<DT>(dq, scale, g.dq, g.dq_rs, q, q < Lq, half);
 }
-template <int HD, bool CAUSAL = false, bool CROSS = false>
-__global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(const AttnOps ops, const bf16_t* __restrict__ o,
-                                                              const bf16_t* __restrict__ dO, const float* __restrict__ lse2,
-                                                              float* __restrict__ delta, const AttnGrads grads, int H, int nblk,
-                                                              float scale, float scale_log2e, int q_begin) {
-    attn_bwd_dq_body<HD, CAUSAL, CROSS>([&]() __attribute__((always_inline)) { return head_ptrs<HD, CROSS>(ops, H, nblk, q_begin); }, o, dO, lse2, delta, grads, scale, scale_log2e, q_begin);
+// The causal backward keeps a launch per kernel: its dK/dV kernel needs the register budget of two waves per SIMD.
+__global__ __launch_bounds__(256, 3) void attn_causal_bwd_dq_kernel(const AttnOps ops, const bf16_t* __restrict__ o,
+                                                                    const bf16_t* __restrict__ dO, const float* __restrict__ lse2,
+                                                                    float* __restrict__ delta, const AttnGrads grads, int H, int nblk,
+                                                                    float scale, float scale_log2e) {
+    attn_bwd_dq_body<64, true, false, true>([&]() __attribute__((always_inline)) { return head_ptrs<64, false>(ops, H, nblk, 0, blockIdx.x, gridDim.x); }, o, dO, lse2, delta, grads, scale, scale_log2e, 0);
 }
 __global__ __launch_bounds__(256, 3) void attn_varlen_bwd_dq_kernel(const AttnOps ops, const SeqTable tab, const bf16_t* __restrict__ o,
                                                                     const bf16_t* __restrict__ dO, const float* __restrict__ lse2,
                                                                     float* __restrict__ delta, const AttnGrads grads, int Hq, int Hkv, int M,
                                                                     float scale, float scale_log2e) {
-    attn_bwd_dq_body<64, false, true>([&]() __attribute__((always_inline)) { return varlen_head_ptrs<64, false>(ops, tab, Hq, Hkv, M); }, o, dO, lse2, delta, grads, scale, scale_log2e, 0);
+    attn_bwd_dq_body<64, false, true, true>([&]() __attribute__((always_inline)) { return varlen_head_ptrs<64, false>(ops, tab, Hq, Hkv, M); }, o, dO, lse2, delta, grads, scale, scale_log2e, 0);
 }
 
 // one 64-query tile of the dK/dV sweep.  LDS buffer: Q tile | dO tile | lse2[64] | delta[64]
@@ -627,12 +644,50 @@ __device__ __forceinline__ void attn_bwd_dkv_body(Heads&& heads, const bf16_t* _
     store_own<DT>(dk, scale, g.dk, g.dk_rs, key, key < Lk, half);
     store_own<DT>(dv, 1.0f, g.dv, g.dv_rs, key, key < Lk, half);
 }
-template <int HD, bool CAUSAL = false, bool CROSS = false>
-__global__ __launch_bounds__(256, CAUSAL ? 2 : 3) void attn_bwd_dkv_kernel(const AttnOps ops, const bf16_t* __restrict__ dO,
-                                                               const float* __restrict__ lse2, const float* __restrict__ delta,
-                                                               const AttnGrads grads, int H, int nblk, float scale, float scale_log2e,
-                                                               int q_begin) {
-    attn_bwd_dkv_body<HD, CAUSAL, CROSS, false>([&]() __attribute__((always_inline)) { return head_ptrs<HD, CROSS>(ops, H, nblk, q_begin); }, dO, lse2, delta, grads, scale, scale_log2e, q_begin);
+__global__ __launch_bounds__(256, 2) void attn_causal_bwd_dkv_kernel(const AttnOps ops, const bf16_t* __restrict__ dO,
+                                                                     const float* __restrict__ lse2, const float* __restrict__ delta,
+                                                                     const AttnGrads grads, int H, int nblk, float scale, float scale_log2e) {
+    attn_bwd_dkv_body<64, true, false, false>([&]() __attribute__((always_inline)) { return head_ptrs<64, false>(ops, H, nblk, 0, blockIdx.x, gridDim.x); }, dO, lse2, delta, grads, scale, scale_log2e, 0);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The non-causal dense and cross backward: attn_delta_kernel, then ONE launch of attn_bwd_kernel whose workgroups take one of two roles.
+// Launched apart, each of the two kernels ran one full generation of resident workgroups and then a sparse second one; in one grid the
+// dQ workgroups fill the slots the dK/dV tail leaves empty.  No workgroup waits for another: the only value one role took from the other
+// was delta, which now comes from the kernel in front.
+// ------------------------------------------------------------------------------------------------
+// delta for the kept queries: the (batch, head, 128-query block) mapping of the dQ role, a wave per 32 queries, no LDS
+template <int HD, bool CROSS>
+__global__ __launch_bounds__(256) void attn_delta_kernel(const AttnOps ops, const bf16_t* __restrict__ o, const bf16_t* __restrict__ dO,
+                                                         float* __restrict__ delta, int H, int nblk, int q_begin) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const HeadPtrs hp = head_ptrs<HD, CROSS>(ops, H, nblk, q_begin, blockIdx.x, gridDim.x);
+    const int q0 = q_begin + hp.blk * 128 + wave * 32;
+    const int Lo = hp.Lq - q_begin;
+    const int q = q0 + (lane & 31);
+    constexpr int KS = AG<HD>::KS;
+    bf16x8 of[KS], dof[KS];
+    const int64_t col = hp.orow * hp.ors + (int64_t)hp.hq * HD;
+    load_own<KS>(dO + col, hp.ors, q0 - q_begin, Lo, lane, dof);
+    load_own<KS>(o + col, hp.ors, q0 - q_begin, Lo, lane, of);
+    const float d = delta_own<KS>(of, dof);
+    if (q < hp.Lq && (lane >> 5) == 0) delta[hp.st_off + q] = d;
+}
+// Workgroups 0 .. n_dkv-1 are the dK/dV role (first, because they run longer), the rest the dQ role.  Each role maps its own (index,
+// count) through head_ptrs, so the blocks of one (batch, head) of a role still share one XCD's chunk.  The hardware deals workgroups to
+// the XCDs by blockIdx.x % 8, so when n_dkv % 8 != 0 the dQ role's chunk c sits on XCD (c + n_dkv) % 8: a rotated set, still one XCD per chunk.
+template <int HD, bool CROSS>
+__global__ __launch_bounds__(256, 3) void attn_bwd_kernel(const AttnOps ops, const bf16_t* __restrict__ dO, const float* __restrict__ lse2,
+                                                          const float* __restrict__ delta, const AttnGrads grads, int H, int nblk_q, int nblk_k,
+                                                          int n_dkv, float scale, float scale_log2e, int q_begin) {
+    const int id = __builtin_amdgcn_readfirstlane(blockIdx.x);
+    if (id < n_dkv)
+        attn_bwd_dkv_body<HD, false, CROSS, false>([&]() __attribute__((always_inline)) { return head_ptrs<HD, CROSS>(ops, H, nblk_k, q_begin, id, n_dkv); },
+                                                   dO, lse2, delta, grads, scale, scale_log2e, q_begin);
+    else
+        attn_bwd_dq_body<HD, false, CROSS, false>([&]() __attribute__((always_inline)) { return head_ptrs<HD, CROSS>(ops, H, nblk_q, q_begin, id - n_dkv, (int)gridDim.x - n_dkv); },
+                                                  nullptr, dO, lse2, delta, grads, scale, scale_log2e, q_begin);
 }
 // Two instantiations.  One query head per KV head: the plain sweep at the dense kernels' three waves per SIMD.  Grouped: the head loop keeps
 // the staging offsets and the store addresses alive through a head's ragged last tile, which the dense kernel runs after they are dead; at
@@ -677,7 +732,13 @@ static void launch_fwd(const AttnOps& ops, int B, int H, int q_begin, void* o, f
                        kScaleLog2e<HD>, q_begin);
 }
 
-template <int HD, bool CAUSAL = false, bool CROSS = false>
+// LDS of a backward workgroup: the dQ role's two K | V buffers, the dK/dV role's two Q | dO | lse2 | delta buffers
+template <int HD>
+constexpr int kDqLds = 4 * AG<HD>::TILE;
+template <int HD>
+constexpr int kDkvLds = 2 * (2 * AG<HD>::TILE + 512);
+
+template <int HD, bool CROSS = false>
 static void launch_bwd(const AttnOps& ops, const void* o, const void* dO, const float* lse2, int B, int H, int q_begin, const AttnGrads& grads,
                        float* delta_ws, hipStream_t s) {
     if (q_begin > 0) {   // packed launches only
@@ -685,10 +746,19 @@ static void launch_bwd(const AttnOps& ops, const void* o, const void* dO, const 
         hipLaunchKernelGGL(zero_q_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, grads.dq, ops.Lq, q_begin, (int64_t)3 * H * HD, H * HD);
     }
     const int nblk_q = (ops.Lq - q_begin + 127) / 128, nblk_k = (ops.Lk + 127) / 128;
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<HD, CAUSAL, CROSS>), dim3(nblk_q * B * H), dim3(256), 4 * AG<HD>::TILE, s, ops, (const bf16_t*)o,
-                       (const bf16_t*)dO, lse2, delta_ws, grads, H, nblk_q, kScale<HD>, kScaleLog2e<HD>, q_begin);
-    hipLaunchKernelGGL((attn_bwd_dkv_kernel<HD, CAUSAL, CROSS>), dim3(nblk_k * B * H), dim3(256), 2 * (2 * AG<HD>::TILE + 512), s, ops,
-                       (const bf16_t*)dO, lse2, delta_ws, grads, H, nblk_k, kScale<HD>, kScaleLog2e<HD>, q_begin);
+    const int n_dq = nblk_q * B * H, n_dkv = nblk_k * B * H;
+    hipLaunchKernelGGL((attn_delta_kernel<HD, CROSS>), dim3(n_dq), dim3(256), 0, s, ops, (const bf16_t*)o, (const bf16_t*)dO, delta_ws, H, nblk_q,
+                       q_begin);
+    hipLaunchKernelGGL((attn_bwd_kernel<HD, CROSS>), dim3(n_dkv + n_dq), dim3(256), kDqLds<HD> > kDkvLds<HD> ? kDqLds<HD> : kDkvLds<HD>, s, ops,
+                       (const bf16_t*)dO, lse2, delta_ws, grads, H, nblk_q, nblk_k, n_dkv, kScale<HD>, kScaleLog2e<HD>, q_begin);
+}
+static void launch_causal_bwd(const AttnOps& ops, const void* o, const void* dO, const float* lse2, int B, int H, const AttnGrads& grads,
+                              float* delta_ws, hipStream_t s) {
+    const int nblk = (ops.Lq + 127) / 128;
+    hipLaunchKernelGGL(attn_causal_bwd_dq_kernel, dim3(nblk * B * H), dim3(256), kDqLds<64>, s, ops, (const bf16_t*)o, (const bf16_t*)dO, lse2,
+                       delta_ws, grads, H, nblk, kScale<64>, kScaleLog2e<64>);
+    hipLaunchKernelGGL(attn_causal_bwd_dkv_kernel, dim3(nblk * B * H), dim3(256), kDkvLds<64>, s, ops, (const bf16_t*)dO, lse2, delta_ws, grads, H,
+                       nblk, kScale<64>, kScaleLog2e<64>);
 }
 
 // every operand is read and every output written 16 bytes per lane (the outputs since the widened stores of round 5)
@@ -700,6 +770,7 @@ static int attn_check(const char* who, int B, int L, int H, int hd, int q_begin)
     VT_CHECK_ARG(hd == 64 || hd == 32, "%s: head_dim %d unsupported (64 or 32)", who, hd);
     VT_CHECK_ARG(B > 0 && L > 0 && H > 0, "%s: bad shape", who);
     VT_CHECK_ARG(q_begin >= 0 && q_begin < L && q_begin % 64 == 0, "%s: q_begin=%d must be a multiple of 64 below L=%d", who, q_begin, L);
+    VT_CHECK_ARG((int64_t)B * H * 2 * (L / 128 + 1) <= 0x7fffffff, "%s: too many workgroups", who);   // the backward's two roles in one grid
     return VT_OK;
 }
 
@@ -754,7 +825,7 @@ extern "C" int vt_attention_causal_bwd(const void* qkv, const void* o, const voi
     VT_CHECK_ARG(qkv && o && dO && lse2 && dqkv && delta_ws, "vt_attention_causal_bwd: null pointer");
     VT_CHECK_ARG(B > 0 && L > 0 && H > 0, "vt_attention_causal_bwd: bad shape");
     VT_CHECK_ARG(attn_aligned(qkv, o, dO, dqkv), "vt_attention_causal_bwd: qkv, o, dO and dqkv must be 16-byte aligned");
-    launch_bwd<64, true>(packed_ops(qkv, L), o, dO, lse2, B, H, 0, packed_grads(dqkv), delta_ws, (hipStream_t)stream);
+    launch_causal_bwd(packed_ops(qkv, L), o, dO, lse2, B, H, packed_grads(dqkv), delta_ws, (hipStream_t)stream);
     VT_CHECK_LAUNCH("vt_attention_causal_bwd");
     return VT_OK;
 }
@@ -766,7 +837,7 @@ extern "C" int vt_attention_causal_bwd(const void* qkv, const void* o, const voi
 static int cross_check(const char* who, int B, int Lq, int Lk, int H, int hd) {
     VT_CHECK_ARG(hd == 64, "%s: head_dim %d unsupported (64)", who, hd);
     VT_CHECK_ARG(B > 0 && Lq > 0 && Lk > 0 && H > 0, "%s: bad shape B=%d Lq=%d Lk=%d H=%d", who, B, Lq, Lk, H);
-    VT_CHECK_ARG((int64_t)B * H * ((Lq > Lk ? Lq : Lk) / 128 + 1) <= 0x7fffffff, "%s: too many workgroups", who);
+    VT_CHECK_ARG((int64_t)B * H * (Lq / 128 + Lk / 128 + 2) <= 0x7fffffff, "%s: too many workgroups", who);   // the backward's two roles in one grid
     return VT_OK;
 }
 static int cross_stride_check(const char* who, const char* what, int64_t rs, int H) {
@@ -807,7 +878,7 @@ extern "C" int vt_attention_cross_bwd(const void* q, int64_t q_rs, const void* k
     VT_CHECK_ARG(attn_aligned(q, k, v, o) && attn_aligned(dO, dq, dk, dv), "%s: q, k, v, o, dO, dq, dk and dv must be 16-byte aligned", who);
     const AttnOps ops{(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, q_rs, k_rs, v_rs, Lq, Lk};
     const AttnGrads grads{(bf16_t*)dq, (bf16_t*)dk, (bf16_t*)dv, dq_rs, dk_rs, dv_rs};
-    launch_bwd<64, false, true>(ops, o, dO, lse2, B, H, 0, grads, delta_ws, (hipStream_t)stream);
+    launch_bwd<64, true>(ops, o, dO, lse2, B, H, 0, grads, delta_ws, (hipStream_t)stream);
     VT_CHECK_LAUNCH(who);
     return VT_OK;
 }
@@ -875,13 +946,13 @@ extern "C" int vt_attention_varlen_bwd(const void* q, int64_t q_rs, const void* 
     VT_CHECK_ARG(attn_aligned(q, k, v, o) && attn_aligned(dO, dq, dk, dv), "%s: q, k, v, o, dO, dq, dk and dv must be 16-byte aligned", who);
     const AttnOps ops{(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, q_rs, k_rs, v_rs, 0, 0};
     const AttnGrads grads{(bf16_t*)dq, (bf16_t*)dk, (bf16_t*)dv, dq_rs, dk_rs, dv_rs};
-    hipLaunchKernelGGL(attn_varlen_bwd_dq_kernel, dim3(tab.total * Hq), dim3(256), 4 * AG<64>::TILE, (hipStream_t)stream, ops, tab, (const bf16_t*)o,
+    hipLaunchKernelGGL(attn_varlen_bwd_dq_kernel, dim3(tab.total * Hq), dim3(256), kDqLds<64>, (hipStream_t)stream, ops, tab, (const bf16_t*)o,
                        (const bf16_t*)dO, lse2, delta_ws, grads, Hq, Hkv, M, kScale<64>, kScaleLog2e<64>);
     if (Hq == Hkv)
-        hipLaunchKernelGGL(attn_varlen_bwd_dkv_kernel<false>, dim3(tab.total * Hkv), dim3(256), 2 * (2 * AG<64>::TILE + 512), (hipStream_t)stream, ops,
+        hipLaunchKernelGGL(attn_varlen_bwd_dkv_kernel<false>, dim3(tab.total * Hkv), dim3(256), kDkvLds<64>, (hipStream_t)stream, ops,
                            tab, (const bf16_t*)dO, lse2, delta_ws, grads, Hq, Hkv, M, kScale<64>, kScaleLog2e<64>);
     else
-        hipLaunchKernelGGL(attn_varlen_bwd_dkv_kernel<true>, dim3(tab.total * Hkv), dim3(256), 2 * (2 * AG<64>::TILE + 512), (hipStream_t)stream, ops,
+        hipLaunchKernelGGL(attn_varlen_bwd_dkv_kernel<true>, dim3(tab.total * Hkv), dim3(256), kDkvLds<64>, (hipStream_t)stream, ops,
                            tab, (const bf16_t*)dO, lse2, delta_ws, grads, Hq, Hkv, M, kScale<64>, kScaleLog2e<64>);
     VT_CHECK_LAUNCH(who);
     return VT_OK;
