@@ -754,9 +754,10 @@ def decode_attention_step(qkv, k_cache, v_cache, pos_dev):
     return o
 
 
-def decode_norm_linear(x, norm_w, eps, W, mode=0):
+def decode_norm_linear(x, norm_w, eps, W, mode=0, out=None):
     """Linear(RMSNorm(x)) for M <= 64 rows in one launch.  x fp32 [M, K]; W bf16 [N, K]; mode 0 -> bf16 [M, N]; mode 1 (W = [w3 ; w1] in
-    8 + 8-row slabs) -> SwiGLU output bf16 [M, N / 2]; mode 2 -> fp32 [M, N] of the bf16-rounded values."""
+    8 + 8-row slabs) -> SwiGLU output bf16 [M, N / 2]; mode 2 -> fp32 [M, N] of the bf16-rounded values.  out: optional destination of
+    that shape and type, rows stride(0) apart (a view of a wider buffer; unit column stride)."""
     require_gpu(x, norm_w, W)
     M, K = x.shape
     N = W.shape[0]
@@ -766,8 +767,13 @@ def decode_norm_linear(x, norm_w, eps, W, mode=0):
         assert x.dtype == torch.float32 and norm_w.dtype == torch.float32
     assert W.dtype == torch.bfloat16 and x.is_contiguous() and W.is_contiguous() and W.shape[1] == K
     cols = N // 2 if mode == 1 else N
-    out = torch.empty(M, cols, device=x.device, dtype=torch.float32 if mode == 2 else torch.bfloat16)
-    check(lib().vt_decode_norm_linear(ptr(x), ptr(norm_w), eps, ptr(W), M, N, K, mode, ptr(out), cols, stream()), "vt_decode_norm_linear")
+    dtype = torch.float32 if mode == 2 else torch.bfloat16
+    if out is None:
+        out = torch.empty(M, cols, device=x.device, dtype=dtype)
+    require_gpu(out)
+    assert out.dtype == dtype and tuple(out.shape) == (M, cols) and out.stride(1) == 1
+    ldo = out.stride(0) if M > 1 else max(out.stride(0), cols)
+    check(lib().vt_decode_norm_linear(ptr(x), ptr(norm_w), eps, ptr(W), M, N, K, mode, ptr(out), ldo, stream()), "vt_decode_norm_linear")
     return out
 
 
