@@ -3,7 +3,10 @@ stack handles and workspaces, parameter tables), for a refactor of that layer th
 listings.  One line per tensor: `<leg> <name> <sha256>`.
 
 Legs: a `tiny` gated FSQ autoencoder (8x32x32 clips, 32 tokens); a tiny `autoencoder_design`; LARP_AR `class_S2` and `class_S2_gqa` training
-step; greedy generation of `class_S2` at the three VT_AR_FUSED_DECODE levels; a 2-block BlockStack, plain and rotary.
+step; greedy generation of `class_S2` at the three VT_AR_FUSED_DECODE levels; a 2-block BlockStack, plain and rotary.  For the layer Functions'
+weight-gradient queue (functional._WeightGrads): `varlen.Attn` on a ragged packed batch (M = 130); a tiny `autoencoder_stat` step; Bottleneck
+and PatchEmbed3D on their own at M = 72; one design block with cross attention, all trainable, with cross_attn.to_gate frozen and with
+self_attn.to_qkv frozen; the `class_S2` step with one w1 frozen.
 
   python tools/host_layer_bits.py > listing.txt
   python tools/host_layer_bits.py --flat-order > order.txt      (no GPU: engine._flat_order of configs `tiny` and `B`)
@@ -123,6 +126,85 @@ def block_stacks():
         report(leg, out, blocks, extra=[("dx", xi.grad)])
 
 
+def step(leg, model, run, x, up, extra=()):
+    """one forward + backward of run(*x) under the loss sum(out * up), from cleared gradients; the inputs' gradients are listed as dx0, dx1, ..."""
+    for p in model.parameters():
+        p.grad = None
+    xs = [t.clone().requires_grad_(True) for t in x]
+    out = run(*xs)
+    (out * up).sum().backward()
+    report(leg, out, model, extra=[(f"dx{i}", t.grad) for i, t in enumerate(xs)] + list(extra))
+
+
+def normal(shape, seed):
+    return torch.from_numpy(gen.normal(shape, seed, 1.0)).cuda()
+
+
+def varlen_attn():
+    """varlen.Attn on a ragged packed batch: sequences of 40 and 90 rows, M = 130, so both weight-gradient problems are row-padded"""
+    torch.manual_seed(12)
+    m = vt.varlen.Attn(128, [2, 1]).cuda()
+    _, cos, sin = vt.varlen.rope_freqs([(2, 4, 4), (5, 4, 4)], [8, 10], device="cuda")
+    step("varlen_attn_ragged", m, lambda x: m(x, (cos, sin), [0, 40, 130], None), [normal((130, 128), 1901)], normal((130, 128), 1902))
+
+
+def stat_autoencoder():
+    """a tiny `autoencoder_stat` training step ('adaptive' stage): StatGate, Linear and ConvTransposePatch"""
+    from tests import stat_reference as S
+    cfg = S.make_cfg("tiny")
+    m = vt.make({"name": "autoencoder_stat", "args": {"bottleneck": None, "prior_model": None, "_geometry": dict(
+        in_grid=[cfg["frames"], cfg["side"], cfg["side"]], patch_size=cfg["patch"], tokens=cfg["tokens"], model_size=cfg["size"])}})
+    m.load_state_dict(S.init_state_dict(cfg), strict=True)
+    m = m.cuda().train()
+    torch.manual_seed(13)
+    video = torch.from_numpy(gen.video_clips(2, 8, 32, 1911)).cuda()
+    up, a, c = normal((2, 3, 8, 32, 32), 1912), normal((2, 32), 1913), normal((2, 32), 1914)
+    out = m(video, current_epoch=0)
+    ((out["pred_frames"] * up).sum() + (out["probs"] * a).sum() + (out["mask"] * c).sum()).backward()
+    report("stat_ae", out["pred_frames"], m, extra=[("probs", out["probs"]), ("mask", out["mask"])])
+
+
+def ragged_projections():
+    """Bottleneck (two functional.Linear around the quantizer) and PatchEmbed3D on their own with M = 2 x 36 = 72 rows: their row padding"""
+    torch.manual_seed(14)
+    b = vt.bottleneck.Bottleneck(16, 128, 128, 36, regularizer={"name": "vq", "args": dict(codebook_size=64, l2_normalized=True)}).cuda()
+    up, wq = normal((2, 36, 128), 1922), normal((3,), 1923)
+
+    def bottleneck(x):
+        o = b(x)
+        return o["output"] + (wq[0] * o["loss_q"] + wq[1] * o["loss_commit"] + wq[2] * o["loss_codebook"]) / up.sum()
+    step("bottleneck_ragged", b, bottleneck, [normal((2, 36, 128), 1921)], up)
+    pe = vt.embed.PatchEmbed3D(spatial_vid_size=48, temporal_vid_size=4, spatial_patch_size=8, temporal_patch_size=4, embed_dim=128).cuda()
+    pos = normal((36, 128), 1933)
+    step("patch_embed_ragged", pe, lambda v: pe(v, pos), [normal((2, 3, 4, 48, 48), 1931)], normal((2, 36, 128), 1932))
+    step("patch_embed_ragged_no_pos", pe, pe, [normal((2, 3, 4, 48, 48), 1931)], normal((2, 36, 128), 1932))
+
+
+def design_blocks_half_frozen():
+    """one design block with cross attention, 2 x 72 rows: one half of a concatenated weight frozen, the other trainable -- one queued
+    problem, one slice returned, one None"""
+    cos, sin = (t.cuda() for t in vt.titok.rope_tables(8, [2, 4, 8]))
+    x, ctx, up = normal((2, 72, 128), 1941), normal((2, 33, 128), 1942), normal((2, 72, 128), 1943)
+    for leg, frozen in (("design_block", ()), ("design_block_cross_gate_frozen", ("cross_attn.to_gate.weight",)),
+                        ("design_block_self_qkv_frozen", ("self_attn.to_qkv.weight",))):
+        torch.manual_seed(15)
+        blk = vt.design.TransformerBlock(128, 2, has_cross_attn=True).cuda()
+        for n in frozen:
+            blk.get_parameter(n).requires_grad_(False)
+        step(leg, blk, lambda xi, ci: blk(xi, (cos, sin), context=ci), [x, ctx], up)
+
+
+def ar_training_w1_frozen():
+    """the class_S2 training step with the first block's w1 frozen beside a trainable w3 (the halves of _FfnBranch's concatenated weight)"""
+    m, cfg, tok, cond = ar_model("class_S2")
+    m.train()
+    m.cls_embedding.dropout_prob = 0.0
+    m.layers[0].feed_forward.w1.weight.requires_grad_(False)
+    logits, loss = m(tok[:, :-1], cond, targets=tok)
+    loss.backward()
+    report("ar_train_class_S2_w1_frozen", logits, m, extra=[("loss", loss)])
+
+
 def flat_order():
     """--flat-order (no GPU needed): (stage, name) of engine._flat_order, the layout of the flat gradient buffer and of the all-reduce slices"""
     from video_tokenizer_amd.engine import _flat_order
@@ -142,3 +224,8 @@ if __name__ == "__main__":
     ar_training("class_S2_gqa")
     ar_generation()
     block_stacks()
+    varlen_attn()
+    stat_autoencoder()
+    ragged_projections()
+    design_blocks_half_frozen()
+    ar_training_w1_frozen()

@@ -17,6 +17,7 @@ fp32 final norm); design.py holds their parameters.
 """
 import ctypes
 import functools
+import inspect
 import operator
 
 import torch
@@ -30,6 +31,69 @@ def _pad64(m):
 
 def _zeros(rows, cols, dev, dtype=torch.bfloat16):
     return torch.zeros(rows, cols, device=dev, dtype=dtype)
+
+
+class _WeightGrads:
+    """The weight gradients of one backward, the Python counterpart of the C++ engine's pending list (vt_engine.hip, flush_wgrads): add()
+    queues dW = dY^T X and returns its fp32 [P, Q] tensor, run() fills all of them with one grouped launch, in the order they were added.  The
+    kernels contract over rows in steps of 64: operands with a ragged row count are zero-padded here, each distinct tensor once per queue."""
+
+    def __init__(self):
+        self.jobs, self.padded = [], {}
+
+    def _rows64(self, t):
+        M = t.shape[0]
+        if M % 64 == 0:
+            return t
+        hit = self.padded.get(id(t))              # (t, copy): holding t keeps its id from being given to another tensor
+        if hit is None:
+            z = torch.zeros(_pad64(M), t.shape[1], device=t.device, dtype=t.dtype)
+            z[:M].copy_(t)
+            hit = self.padded[id(t)] = (t, z)
+        return hit[1]
+
+    def add(self, dY, X, want=True):
+        if not want:
+            return None
+        out = torch.empty(dY.shape[1], X.shape[1], device=dY.device)
+        self.jobs.append(dict(A=self._rows64(dY), B=self._rows64(X), out=out))
+        return out
+
+    def run(self):
+        for i in range(0, len(self.jobs), hip.TN_MAX_GROUP):
+            hip.gemm_tn_grouped(self.jobs[i:i + hip.TN_MAX_GROUP])
+
+
+def _split_rows(dw, n):
+    """the gradients of the two weights a GEMM ran concatenated along N: rows [:n] and [n:] of dw (None stays None)"""
+    return (None, None) if dw is None else (dw[:n], dw[n:])
+
+
+@functools.lru_cache(maxsize=None)
+def _forward_args(cls):
+    """{argument name of cls.forward behind ctx: its position}, read once per Function class"""
+    return {name: i for i, name in enumerate(tuple(inspect.signature(cls.forward).parameters)[1:])}
+
+
+@functools.lru_cache(maxsize=None)
+def _need_table(cls, needs):
+    return dict(zip(_forward_args(cls), needs))
+
+
+def _needs(ctx, cls):
+    """ctx.needs_input_grad by the name of the forward's argument: a table shared by every backward of the class with this pattern, to read only"""
+    return _need_table(cls, ctx.needs_input_grad)
+
+
+def _grads(ctx, cls, **named):
+    """the return tuple of cls.backward: the gradients given by argument name, in the forward's order; None where none was given or needed.
+    A name the forward does not have is a KeyError.  (A few look-ups per call: the steps of these layers are bound by the host.)"""
+    position, need = _forward_args(cls), ctx.needs_input_grad
+    out = [None] * len(need)
+    for name, g in named.items():
+        i = position[name]
+        out[i] = g if need[i] else None
+    return tuple(out)
 
 
 # The parameters of one block / one gated layer, in the field order of the C structs: the only spelling of either list.
@@ -241,26 +305,20 @@ class PatchEmbed(torch.autograd.Function):
     def backward(ctx, dtok):
         patches, wt = ctx.saved_tensors
         B, C, T, S, pt, p, D = ctx.geom
-        M, Kp = patches.shape
-        Mp = _pad64(M)
-        dev = dtok.device
-        dT = _zeros(Mp, D, dev)
-        hip.cast_rows(dtok.contiguous().reshape(M, D), dst=dT)
+        M = patches.shape[0]
+        need = _needs(ctx, PatchEmbed)
+        dT = hip.cast_rows(dtok.contiguous().reshape(M, D))
         dvideo = dw = db = None
-        if ctx.needs_input_grad[0]:
-            rows = hip.gemm_nt(dT[:M], wt, hip.EPI_F32)            # [M, Kp] fp32 in patch order
+        if need["video"]:
+            rows = hip.gemm_nt(dT, wt, hip.EPI_F32)                # [M, Kp] fp32 in patch order
             dvideo = hip.unpatchify(rows, B, C, T, S, pt, p)
-        if ctx.needs_input_grad[1]:
-            pp = patches
-            if Mp != M:
-                pp = _zeros(Mp, Kp, dev)
-                pp[:M].copy_(patches)
-            dw = torch.empty(D, Kp, device=dev)
-            hip.gemm_tn_grouped([dict(A=dT, B=pp, out=dw)])
-            dw = dw.reshape(D, C, pt, p, p)
-        if ctx.needs_input_grad[2]:
+        if need["weight"]:
+            wg = _WeightGrads()
+            dw = wg.add(dT, patches).reshape(D, C, pt, p, p)
+            wg.run()
+        if need["bias"]:
             db = hip.colsum(dT, rows=M)
-        return dvideo, dw, db, None
+        return _grads(ctx, PatchEmbed, video=dvideo, weight=dw, bias=db)
 
 
 def _pad_cols(t2d, k_to):
@@ -282,33 +340,32 @@ class Linear(torch.autograd.Function):
         x2 = x.reshape(-1, shp[-1]).float()
         M, K = x2.shape
         N = weight.shape[0]
-        Kp_, Np_, Mp = _pad64(K), _pad64(N), _pad64(M)
-        xb = _zeros(Mp, Kp_, x.device)
-        xb[:M, :K].copy_(x2)
+        Kp_, Np_ = _pad64(K), _pad64(N)
+        xb = _pad_cols(x2, Kp_)
         wb = _pad_cols(weight.detach(), Kp_)                        # [N, Kp]
-        y = hip.gemm_nt(xb[:M], wb, hip.EPI_F32, bias=bias, round_bf16=True, out=torch.empty(M, (N + 3) // 4 * 4, device=x.device))
+        y = hip.gemm_nt(xb, wb, hip.EPI_F32, bias=bias, round_bf16=True, out=torch.empty(M, (N + 3) // 4 * 4, device=x.device))
         ctx.save_for_backward(xb, weight)
-        ctx.geom = (shp, M, K, N, Kp_, Np_, Mp)
+        ctx.geom = (shp, M, K, N, Np_)
         return y[:, :N].reshape(*shp[:-1], N)
 
     @staticmethod
     def backward(ctx, dy):
         xb, weight = ctx.saved_tensors
-        shp, M, K, N, Kp_, Np_, Mp = ctx.geom
-        dev = dy.device
-        dyb = _zeros(Mp, Np_, dev)                                  # grad of a bf16 output is bf16 under autocast
-        dyb[:M, :N].copy_(dy.reshape(M, N))
+        shp, M, K, N, Np_ = ctx.geom
+        need = _needs(ctx, Linear)
+        dyb = _pad_cols(dy.reshape(M, N), Np_)                      # grad of a bf16 output is bf16 under autocast
         dx = dw = db = None
-        if ctx.needs_input_grad[0]:
+        if need["x"]:
             wt = _pad_cols(weight.detach().t().contiguous(), Np_)   # [K, Np]: B operand of dX = dY . W
-            dx = hip.gemm_nt(dyb[:M], wt, hip.EPI_F32, out=torch.empty(M, (K + 3) // 4 * 4, device=dev))[:, :K].reshape(shp)
-        if ctx.needs_input_grad[1]:
-            full = torch.empty(Np_, Kp_, device=dev)
-            hip.gemm_tn_grouped([dict(A=dyb, B=xb, out=full)])
+            dx = hip.gemm_nt(dyb, wt, hip.EPI_F32, out=torch.empty(M, (K + 3) // 4 * 4, device=dy.device))[:, :K].reshape(shp)
+        if need["weight"]:
+            wg = _WeightGrads()
+            full = wg.add(dyb, xb)                                  # [Np, Kp]
+            wg.run()
             dw = full[:N, :K].contiguous()
-        if ctx.needs_input_grad[2]:
+        if need["bias"]:
             db = hip.colsum(dyb, rows=M)[:N].contiguous()
-        return dx, dw, db
+        return _grads(ctx, Linear, x=dx, weight=dw, bias=db)
 
 
 class VectorQuantize(torch.autograd.Function):
@@ -410,7 +467,7 @@ class LayerNormRows(torch.autograd.Function):
         x2, weight, mean, rstd = ctx.saved_tensors
         dyb = hip.cast_rows(dy.contiguous().reshape(x2.shape).float())
         dx, _, dg, db, _ = hip.layernorm_bwd(dyb, x2, weight, mean, rstd, want_dxsum=False)
-        return dx.reshape(dy.shape), dg, db, None
+        return _grads(ctx, LayerNormRows, x=dx.reshape(dy.shape), weight=dg, bias=db)
 
 
 class Unpatchify(torch.autograd.Function):
@@ -432,19 +489,6 @@ class Unpatchify(torch.autograd.Function):
 # ------------------------------------------------------------------------------------------------------------------------
 # cross attention and model_design's CrossAttention layer (models/model_design/base/transformer.py:92-141)
 # ------------------------------------------------------------------------------------------------------------------------
-def _rows64(*ts):
-    """the weight-gradient GEMMs contract over rows in steps of 64: zero-padded copies of ragged row counts"""
-    M = ts[0].shape[0]
-    if M % 64 == 0:
-        return ts
-    out = []
-    for t in ts:
-        z = torch.zeros(_pad64(M), t.shape[1], device=t.device, dtype=t.dtype)
-        z[:M].copy_(t)
-        out.append(z)
-    return out
-
-
 class CrossAttend(torch.autograd.Function):
     """softmax(q k^T / 8) v, head_dim 64, no mask, on vt_attention_cross_*: q a bf16 view [B * Lq, 64 H], k and v bf16 views [B * Lk, 64 H],
     each with a row stride of its own (column blocks of wider projections are read in place) -> o bf16 [B * Lq, 64 H]"""
@@ -498,7 +542,7 @@ class CrossAttentionLayer(torch.autograd.Function):
         B, Lq, Lk, D, Dc, H, eps = ctx.geom
         Mq, Mk = B * Lq, B * Lk
         dev = dout.device
-        need = ctx.needs_input_grad
+        need = _needs(ctx, CrossAttentionLayer)
         gb = hip.cast_rows(dout.contiguous().reshape(Mq, D).float())
         dog = hip.gemm_nt(gb, wo_t, hip.EPI_BF16)
         dqg = torch.empty(Mq, 2 * D, device=dev, dtype=torch.bfloat16)   # gradient of [q | gate], every column written below
@@ -509,30 +553,15 @@ class CrossAttentionLayer(torch.autograd.Function):
         _, dkn_w = hip.head_rmsnorm_bwd(dkv[:, :D], kv[:, :D], kn_w, eps, H, dx=dkv[:, :D])      # in place
         dxn = hip.gemm_nt(dqg, wqg_t, hip.EPI_BF16)
         dcn = hip.gemm_nt(dkv, wkv_t, hip.EPI_BF16)
-        dwq = dwg = dwkv = dwo = None
-        jobs = []
-        if need[4] or need[6]:
-            dwqg = torch.empty(2 * D, D, device=dev)
-            dqg_, xn_ = _rows64(dqg, xn)
-            jobs.append(dict(A=dqg_, B=xn_, out=dwqg))
-        if need[5]:
-            dwkv = torch.empty(2 * D, Dc, device=dev)
-            dkv_, cn_ = _rows64(dkv, cn)
-            jobs.append(dict(A=dkv_, B=cn_, out=dwkv))
-        if need[9]:
-            dwo = torch.empty(D, D, device=dev)
-            gb_, og_ = _rows64(gb, og)
-            jobs.append(dict(A=gb_, B=og_, out=dwo))
-        if jobs:
-            hip.gemm_tn_grouped(jobs)
-        if need[4]:
-            dwq = dwqg[:D].contiguous()
-        if need[6]:
-            dwg = dwqg[D:].contiguous()
+        wg = _WeightGrads()
+        dwq, dwg = _split_rows(wg.add(dqg, xn, need["to_q_w"] or need["to_gate_w"]), D)
+        dwkv = wg.add(dkv, cn, need["to_kv_w"])
+        dwo = wg.add(gb, og, need["out_proj_w"])
+        wg.run()
         dx, _, dnq_w = hip.rmsnorm_any_bwd(dxn, x2, nq_w, rstd_x)
         dc, _, dnkv_w = hip.rmsnorm_any_bwd(dcn, c2, nkv_w, rstd_c)
-        return (dx.reshape(B, Lq, D) if need[0] else None, dc.reshape(B, Lk, Dc) if need[1] else None, dnq_w if need[2] else None,
-                dnkv_w if need[3] else None, dwq, dwkv, dwg, dqn_w if need[7] else None, dkn_w if need[8] else None, dwo, None, None, None, None, None)
+        return _grads(ctx, CrossAttentionLayer, x=dx.reshape(B, Lq, D), context=dc.reshape(B, Lk, Dc), norm_q_w=dnq_w, norm_kv_w=dnkv_w, to_q_w=dwq,
+                      to_kv_w=dwkv, to_gate_w=dwg, q_norm_w=dqn_w, k_norm_w=dkn_w, out_proj_w=dwo)
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -558,8 +587,8 @@ class ResidualScale(torch.autograd.Function):
     def backward(ctx, dout):
         y2, s = ctx.saved_tensors
         d2 = dout.contiguous().reshape(y2.shape).float()
-        dy, ds = hip.residual_scale_bwd(d2, y2, s, want_ds=ctx.needs_input_grad[2])
-        return dout, dy.reshape(dout.shape) if ctx.needs_input_grad[1] else None, ds
+        dy, ds = hip.residual_scale_bwd(d2, y2, s, want_ds=_needs(ctx, ResidualScale)["scale"])
+        return _grads(ctx, ResidualScale, x=dout, y=dy.reshape(dout.shape), scale=ds)
 
 
 class RMSNormRows(torch.autograd.Function):
@@ -581,7 +610,7 @@ class RMSNormRows(torch.autograd.Function):
     def backward(ctx, dy):
         x2, w, rstd = ctx.saved_tensors
         dx, _, dw = getattr(hip, ctx.family + "_bwd")(hip.cast_rows(dy.contiguous().reshape(x2.shape).float()), x2, w, rstd)
-        return dx.reshape(dy.shape), dw if ctx.needs_input_grad[1] else None, None, None
+        return _grads(ctx, RMSNormRows, x=dx.reshape(dy.shape), weight=dw)
 
 
 class RMSNormF32(torch.autograd.Function):
@@ -600,7 +629,7 @@ class RMSNormF32(torch.autograd.Function):
     def backward(ctx, dy):
         x2, w, rstd = ctx.saved_tensors
         dx, dw = hip.rmsnorm_any_f32_bwd(dy.contiguous().reshape(x2.shape).float(), x2, w, rstd)
-        return dx.reshape(dy.shape), dw if ctx.needs_input_grad[1] else None, None
+        return _grads(ctx, RMSNormF32, x=dx.reshape(dy.shape), weight=dw)
 
 
 class SelfAttentionLayer(torch.autograd.Function):
@@ -635,36 +664,23 @@ class SelfAttentionLayer(torch.autograd.Function):
         x2, n_w, qn_w, kn_w, s, cos, sin, rstd, xn, qkvg, qkv, o, lse2, og, y, wqkvg_t, wo_t = ctx.saved_tensors
         B, L, D, H, eps = ctx.geom
         M = B * L
-        dev = dout.device
-        need = ctx.needs_input_grad
+        need = _needs(ctx, SelfAttentionLayer)
         d2 = dout.contiguous().reshape(M, D).float()
-        dy, ds = hip.residual_scale_bwd(d2, y, s, want_ds=need[3])
+        dy, ds = hip.residual_scale_bwd(d2, y, s, want_ds=need["res_scale"])
         gb = hip.cast_rows(dy)                                           # exact: dy holds bf16 values
         dog = hip.gemm_nt(gb, wo_t, hip.EPI_BF16)
-        dqkvg = torch.empty(M, 4 * D, device=dev, dtype=torch.bfloat16)  # gradient of [q | k | v | gate], every column written below
+        dqkvg = torch.empty(M, 4 * D, device=dout.device, dtype=torch.bfloat16)  # gradient of [q | k | v | gate], every column written below
         d_o = hip.sigmoid_gate_bwd(dog, o, qkvg, dqkvg)
         dqkv = hip.attention_bwd(qkv, o, d_o, lse2, B, L, H)
-        dqn_w, dkn_w = hip.qkrms_rope_bwd(qkvg, dqkv, L, H, qn_w, kn_w, eps, cos, sin, dqkvg, want_dw=need[7] or need[8])
+        dqn_w, dkn_w = hip.qkrms_rope_bwd(qkvg, dqkv, L, H, qn_w, kn_w, eps, cos, sin, dqkvg, want_dw=need["q_norm_w"] or need["k_norm_w"])
         dxn = hip.gemm_nt(dqkvg, wqkvg_t, hip.EPI_BF16)                  # the gradients from to_qkv and to_gate summed in fp32, rounded once
-        dwqkv = dwg = dwo = None
-        jobs = []
-        if need[5] or need[6]:
-            dwqkvg = torch.empty(4 * D, D, device=dev)
-            a_, b_ = _rows64(dqkvg, xn)
-            jobs.append(dict(A=a_, B=b_, out=dwqkvg))
-        if need[9]:
-            dwo = torch.empty(D, D, device=dev)
-            a_, b_ = _rows64(gb, og)
-            jobs.append(dict(A=a_, B=b_, out=dwo))
-        if jobs:
-            hip.gemm_tn_grouped(jobs)
-        if need[5]:
-            dwqkv = dwqkvg[:3 * D].contiguous()
-        if need[6]:
-            dwg = dwqkvg[3 * D:].contiguous()
+        wg = _WeightGrads()
+        dwqkv, dwg = _split_rows(wg.add(dqkvg, xn, need["to_qkv_w"] or need["to_gate_w"]), 3 * D)
+        dwo = wg.add(gb, og, need["out_proj_w"])
+        wg.run()
         dx, _, dn_w = hip.rmsnorm_any_bwd(dxn, x2, n_w, rstd, dres=d2)   # + the residual path's gradient
-        return (dx.reshape(B, L, D) if need[0] else None, None, None, ds, dn_w if need[4] else None, dwqkv, dwg, dqn_w if need[7] else None,
-                dkn_w if need[8] else None, dwo, None, None, None, None)
+        return _grads(ctx, SelfAttentionLayer, x=dx.reshape(B, L, D), res_scale=ds, norm_w=dn_w, to_qkv_w=dwqkv, to_gate_w=dwg, q_norm_w=dqn_w,
+                      k_norm_w=dkn_w, out_proj_w=dwo)
 
 
 class FeedForwardLayer(torch.autograd.Function):
@@ -694,31 +710,20 @@ class FeedForwardLayer(torch.autograd.Function):
     def backward(ctx, dout):
         x2, n_w, s, rstd, xn, h, a, y, w1_t, w2_t = ctx.saved_tensors
         M, D = x2.shape
-        inner = ctx.inner
-        dev = dout.device
-        need = ctx.needs_input_grad
+        need = _needs(ctx, FeedForwardLayer)
         d2 = dout.contiguous().reshape(M, D).float()
-        dy, ds = hip.residual_scale_bwd(d2, y, s, want_ds=need[1])
+        dy, ds = hip.residual_scale_bwd(d2, y, s, want_ds=need["res_scale"])
         gb = hip.cast_rows(dy)
         da = hip.gemm_nt(gb, w2_t, hip.EPI_BF16)                        # [M, pad64(inner)]
         dh = hip.geglu_bwd(da, h)
         dxn = hip.gemm_nt(dh, w1_t, hip.EPI_BF16)
-        dw1 = dw2 = None
-        jobs = []
-        if need[3]:
-            dw1 = torch.empty(2 * inner, D, device=dev)
-            a_, b_ = _rows64(dh, xn)
-            jobs.append(dict(A=a_, B=b_, out=dw1))
-        if need[4]:
-            dw2p = torch.empty(D, a.shape[1], device=dev)
-            a_, b_ = _rows64(gb, a)
-            jobs.append(dict(A=a_, B=b_, out=dw2p))
-        if jobs:
-            hip.gemm_tn_grouped(jobs)
-        if need[4]:
-            dw2 = dw2p[:, :inner].contiguous()
+        wg = _WeightGrads()
+        dw1 = wg.add(dh, xn, need["fc1_w"])
+        dw2p = wg.add(gb, a, need["fc2_w"])                             # [D, pad64(inner)]
+        wg.run()
+        dw2 = dw2p[:, :ctx.inner].contiguous() if need["fc2_w"] else None
         dx, _, dn_w = hip.rmsnorm_any_bwd(dxn, x2, n_w, rstd, dres=d2)
-        return dx.reshape(dout.shape) if need[0] else None, ds, dn_w if need[2] else None, dw1, dw2, None, None, None
+        return _grads(ctx, FeedForwardLayer, x=dx.reshape(dout.shape), res_scale=ds, norm_w=dn_w, fc1_w=dw1, fc2_w=dw2)
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -776,27 +781,17 @@ class VarlenAttentionLayer(torch.autograd.Function):
         cu, Hq, Hkv, eps = ctx.geom
         M, D = x2.shape
         G = 64 * Hkv
-        dev = dout.device
-        need = ctx.needs_input_grad
+        need = _needs(ctx, VarlenAttentionLayer)
         gb = hip.cast_rows(dout.contiguous().float())
         d_o = hip.gemm_nt(gb, wo_t, hip.EPI_BF16)
-        dqkr = torch.empty(M, D + 2 * G, device=dev, dtype=torch.bfloat16)  # gradient of the rotated [q | k | v], every column written below
+        dqkr = torch.empty(M, D + 2 * G, device=dout.device, dtype=torch.bfloat16)  # gradient of the rotated [q | k | v], every column written below
         hip.attention_varlen_bwd(qkr[:, :D], qkr[:, D:D + G], qkr[:, D + G:], o, d_o, lse2, cu, Hq, Hkv, dq=dqkr[:, :D], dk=dqkr[:, D:D + G],
                                  dv=dqkr[:, D + G:])
         dqkv, (dq_w, dq_b, dk_w, dk_b) = hip.qknorm_rope_gqa_bwd(qkv, dqkr, Hq, Hkv, qw, kw, eps, cos, sin)
         dxn = hip.gemm_nt(dqkv, wqkv_t, hip.EPI_BF16)
-        dwqkv = dwo = None
-        jobs = []
-        if need[6]:
-            dwqkv = torch.empty(D + 2 * G, D, device=dev)
-            a_, b_ = _rows64(dqkv, xn)
-            jobs.append(dict(A=a_, B=b_, out=dwqkv))
-        if need[11]:
-            dwo = torch.empty(D, D, device=dev)
-            a_, b_ = _rows64(gb, o)
-            jobs.append(dict(A=a_, B=b_, out=dwo))
-        if jobs:
-            hip.gemm_tn_grouped(jobs)
+        wg = _WeightGrads()
+        dwqkv = wg.add(dqkv, xn, need["to_qkv_w"])
+        dwo = wg.add(gb, o, need["out_proj_w"])
+        wg.run()
         dx, _, dg, db, _ = hip.layernorm_bwd(dxn, x2, pw, mean, rstd, want_dxsum=False, want_dxb=False)
-        return (dx if need[0] else None, None, None, None, dg if need[4] else None, db if need[5] else None, dwqkv, dq_w if need[7] else None,
-                dq_b if need[8] else None, dk_w if need[9] else None, dk_b if need[10] else None, dwo, None, None, None, None, None)
+        return _grads(ctx, VarlenAttentionLayer, x=dx, pre_w=dg, pre_b=db, to_qkv_w=dwqkv, q_w=dq_w, q_b=dq_b, k_w=dk_w, k_b=dk_b, out_proj_w=dwo)

@@ -27,7 +27,7 @@ import torch.nn.functional as F
 from . import hip, packs
 from .embed import get_1d_sincos_pos_embed_from_grid
 from .functional import Linear as LinearFn
-from .functional import RMSNormRows, _rows64
+from .functional import RMSNormRows, _grads, _needs, _split_rows, _WeightGrads
 from .pretrained import LocalPretrainedMixin
 from .registry import models as _registry
 
@@ -104,17 +104,17 @@ class _AttnBranch(torch.autograd.Function):
     def backward(ctx, dout):
         x2, norm_w, rstd, y, qkv, o, lse, wqkv_t, wo_t = ctx.saved_tensors
         B, L, D, H = ctx.geom
-        M = B * L
-        dev = dout.device
-        gb = hip.cast_rows(dout.contiguous().reshape(M, D).float())
+        need = _needs(ctx, _AttnBranch)
+        gb = hip.cast_rows(dout.contiguous().reshape(B * L, D).float())
         d_o = hip.gemm_nt(gb, wo_t, hip.EPI_BF16)
         dqkv = hip.attention_causal_bwd(qkv, o, d_o, lse, B, L, H)
         dy = hip.gemm_nt(dqkv, wqkv_t, hip.EPI_BF16)
-        dwo, dwqkv = torch.empty(D, D, device=dev), torch.empty(3 * D, D, device=dev)
-        gb_, o_, dqkv_, y_ = _rows64(gb, o, dqkv, y)
-        hip.gemm_tn_grouped([dict(A=gb_, B=o_, out=dwo), dict(A=dqkv_, B=y_, out=dwqkv)])
+        wg = _WeightGrads()
+        dwo = wg.add(gb, o, need["wo"])
+        dwqkv = wg.add(dqkv, y, need["wqkv"])
+        wg.run()
         dx, _, dnw = hip.rmsnorm_bwd(dy, x2, norm_w, rstd)
-        return dx.reshape(B, L, D), dnw, dwqkv, dwo, None, None, None, None
+        return _grads(ctx, _AttnBranch, x=dx.reshape(B, L, D), norm_w=dnw, wqkv=dwqkv, wo=dwo)
 
 
 class _FfnBranch(torch.autograd.Function):
@@ -138,17 +138,17 @@ class _FfnBranch(torch.autograd.Function):
     def backward(ctx, dout):
         x2, norm_w, rstd, y, h, a, w31_t, w2_t = ctx.saved_tensors
         B, L, D, I = ctx.geom
-        M = B * L
-        dev = dout.device
-        gb = hip.cast_rows(dout.contiguous().reshape(M, D).float())
+        need = _needs(ctx, _FfnBranch)
+        gb = hip.cast_rows(dout.contiguous().reshape(B * L, D).float())
         da = hip.gemm_nt(gb, w2_t, hip.EPI_BF16)
         dh = hip.swiglu_bwd(da, h)
         dy = hip.gemm_nt(dh, w31_t, hip.EPI_BF16)
-        dw2, dw31 = torch.empty(D, I, device=dev), torch.empty(2 * I, D, device=dev)
-        gb_, a_, dh_, y_ = _rows64(gb, a, dh, y)
-        hip.gemm_tn_grouped([dict(A=gb_, B=a_, out=dw2), dict(A=dh_, B=y_, out=dw31)])
+        wg = _WeightGrads()
+        dw2 = wg.add(gb, a, need["w2"])
+        dw3, dw1 = _split_rows(wg.add(dh, y, need["w1"] or need["w3"]), I)
+        wg.run()
         dx, _, dnw = hip.rmsnorm_bwd(dy, x2, norm_w, rstd)
-        return dx.reshape(B, L, D), dnw, dw31[I:].contiguous(), dw31[:I].contiguous(), dw2, None, None, None
+        return _grads(ctx, _FfnBranch, x=dx.reshape(B, L, D), norm_w=dnw, w1=dw1, w3=dw3, w2=dw2)
 
 
 # ------------------------------------------------------------------------------------------------ modules (the reference's tree)

@@ -35,7 +35,7 @@ from torch import nn
 
 from . import hip
 from .fsq import FSQ
-from .functional import Linear as LinearFn, PatchEmbed as PatchEmbedFn, Unpatchify as UnpatchifyFn
+from .functional import Linear as LinearFn, PatchEmbed as PatchEmbedFn, Unpatchify as UnpatchifyFn, _grads, _needs, _WeightGrads
 from .registry import register
 from .titok import ResidualAttentionBlock, _RopeMixin, get_model_dims, init_weights, rope_tables
 
@@ -85,24 +85,22 @@ class StatGate(torch.autograd.Function):
         xb, w1t, u, g, z2, mask, probs, w2f = ctx.saved_tensors
         xshape, zshape, levels, ste, scale = ctx.cfg
         M, W = g.shape
-        dev = g.device
         dc = None
         if z2 is not None:
             dc = dcodes.reshape(z2.shape).float().contiguous() if dcodes is not None else torch.zeros_like(z2)
         dp = dprobs.reshape(M).float().contiguous() if dprobs is not None else None
         dm = dmask.reshape(M).float().contiguous() if (dmask is not None and ste) else None
         dU, dz, dw2, db2 = hip.stat_gate_backward(dc, dp, dm, z2, mask, probs, u, g, w2f, levels, ste)
-        need = ctx.needs_input_grad
-        dx = dw1 = db1 = None
-        if need[0]:
+        need = _needs(ctx, StatGate)
+        dx = db1 = None
+        if need["x"]:
             dx = hip.gemm_nt(dU, w1t, hip.EPI_F32, out_scale=scale if scale != 1.0 else 0.0).reshape(xshape)
-        if need[2]:
-            dw1 = torch.empty(W, W, device=dev)
-            hip.gemm_tn_grouped([dict(A=dU, B=xb, out=dw1)])
-        if need[3]:
+        wg = _WeightGrads()
+        dw1 = wg.add(dU, xb, need["w1"])
+        wg.run()
+        if need["b1"]:
             db1 = hip.colsum(dU, rows=M)
-        dzo = dz.reshape(zshape) if (dz is not None and need[1]) else None
-        return dx, dzo, dw1, db1, dw2.reshape(1, W) if need[4] else None, db2 if need[5] else None, None, None, None, None, None
+        return _grads(ctx, StatGate, x=dx, z=dz.reshape(zshape) if dz is not None else None, w1=dw1, b1=db1, w2=dw2.reshape(1, W), b2=db2)
 
 
 class ProbPredictor(nn.Module):

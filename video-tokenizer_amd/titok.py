@@ -25,7 +25,7 @@ from torch import nn
 
 from . import hip, packs
 from .fsq import FSQ
-from .functional import GatedStack, LayerNormRows, Linear as LinearFn, PatchEmbed as PatchEmbedFn, gated_params, rotary_block_stack
+from .functional import GatedStack, LayerNormRows, Linear as LinearFn, PatchEmbed as PatchEmbedFn, _grads, _needs, _WeightGrads, gated_params, rotary_block_stack
 from .registry import register
 
 
@@ -130,15 +130,18 @@ class ConvTransposePatch(torch.autograd.Function):
     def backward(ctx, dvideo):
         xb, wt = ctx.saved_tensors
         B, C, T, S, pt, p = ctx.geom
-        dev = dvideo.device
+        need = _needs(ctx, ConvTransposePatch)
         drows = hip.patchify(dvideo.contiguous().float(), pt, p)              # bf16 [M, Kp], (c, dt, dy, dx) inside a patch
-        M, Kp = drows.shape
+        M = drows.shape[0]
         width = xb.shape[1]
         dtok = hip.gemm_nt(drows, wt, hip.EPI_F32, round_bf16=True)            # [M, width]
-        dw = torch.empty(width, Kp, device=dev)
-        hip.gemm_tn_grouped([dict(A=xb, B=drows, out=dw)])
+        wg = _WeightGrads()
+        dw = wg.add(xb, drows, need["weight"])
+        wg.run()
         db = hip.colsum(drows, rows=M).reshape(C, pt * p * p).sum(dim=1)
-        return dtok.reshape(B, M // B, width), dw.reshape(width, C, pt, p, p), db, None
+        if dw is not None:
+            dw = dw.reshape(width, C, pt, p, p)
+        return _grads(ctx, ConvTransposePatch, tok=dtok.reshape(B, M // B, width), weight=dw, bias=db)
 
 
 class GEGLU(nn.Module):
