@@ -254,6 +254,42 @@ int vt_attention_varlen_bwd(const void* q, int64_t q_rs, const void* k, int64_t 
                             int32_t Hkv, int32_t hd, void* dq, int64_t dq_rs, void* dk, int64_t dk_rs, void* dv, int64_t dv_rs, float* delta_ws,
                             vtStream stream);
 
+/* Data movement of the packed `titok` model (models/model_titok/base/blocks.py:82-222; csrc/vt_packed.hip).  Every table is a HOST array,
+ * read and validated before the call returns, and travels to the kernel by value in its arguments (as cu_seqlens_host above): at most
+ * VT_VARLEN_MAX_SEQ entries, no kernel reads a boundary or a pointer table from device memory, the launches can be captured in a graph.
+ * No atomics: every result has the same bits on every run.  A violation returns VT_ERR_INVALID, vt_last_error names the entry point and
+ * the offending value, and nothing is launched.
+ *
+ * vt_patchify_clips: n clips, clip b its own contiguous fp32 [C, T_b, H_b, W_b] at the 16-byte aligned device pointer clips_host[b].data,
+ * -> bf16 patch rows [sum_b G_b, Kp], G_b = (T_b/pt)(H_b/p)(W_b/p), Kp = C*pt*p*p; column order (c, dt, dy, dx) and token order (t, h, w)
+ * as vt_patchify; clip b starts at row sum_{a<b} G_a; one launch.  H_b != W_b is fine; p % 8 == 0, T_b % pt == 0, H_b % p == 0 and
+ * W_b % p == 0 are required, and `rows` must be sum_b G_b (the row count the caller allocated).
+ * vt_unpatchify_clips: the inverse on fp32 rows [sum_b G_b, Kp], written into the n clips. */
+typedef struct {
+    void* data;        /* device pointer, fp32 [C, T, H, W] contiguous, 16-byte aligned */
+    int32_t T, H, W;
+} vtClip;
+int vt_patchify_clips(const vtClip* clips_host, int32_t n, int32_t C, int32_t pt, int32_t p, void* rows_bf16, int64_t rows, vtStream stream);
+int vt_unpatchify_clips(const float* rows_f32, int64_t rows, const vtClip* clips_host, int32_t n, int32_t C, int32_t pt, int32_t p,
+                        vtStream stream);
+/* A packed fp32 [M, D] in which sequence b is rows cu[b] .. cu[b+1]-1 and splits after its first lead[b] rows into a lead and a tail
+ * segment (the encoder's [latent tokens | patch rows], the decoder's [codes | mask tokens]).  `which` chooses one of the two.
+ * cu[0] == 0, strictly increasing, cu[n_seq] == M; 1 <= lead[b] < cu[b+1] - cu[b] (both segments non-empty); 1 <= n_seq <=
+ * VT_VARLEN_MAX_SEQ; D % 4 == 0; every pointer 16-byte aligned.
+ * vt_packed_scatter: every row of dst [M, D] is written: the chosen segments take, in order, the rows of the compact src
+ * [sum_b |segment_b|, D]; the rows of the other segments take vec[D], or zeros when vec is NULL.
+ * vt_packed_gather: out compact [sum_b |segment_b|, D] = the chosen segments' rows of packed, in order.
+ * vt_packed_segment_colsum: out[D] = the sum over every row of the chosen segments, in a fixed order (slabs of consecutive rows, then
+ * the slabs in order), read in place; workspace: vt_packed_segment_colsum_workspace_bytes(D) bytes. */
+enum { VT_PACKED_LEAD = 0, VT_PACKED_TAIL = 1 };
+int vt_packed_scatter(const float* src, const float* vec, const int32_t* cu_seqlens_host, const int32_t* lead_host, int32_t n_seq, int32_t M,
+                      int32_t D, int32_t which, float* dst, vtStream stream);
+int vt_packed_gather(const float* packed, const int32_t* cu_seqlens_host, const int32_t* lead_host, int32_t n_seq, int32_t M, int32_t D,
+                     int32_t which, float* out, vtStream stream);
+size_t vt_packed_segment_colsum_workspace_bytes(int32_t D);
+int vt_packed_segment_colsum(const float* packed, const int32_t* cu_seqlens_host, const int32_t* lead_host, int32_t n_seq, int32_t M, int32_t D,
+                             int32_t which, float* out, void* workspace, vtStream stream);
+
 /* ------------------------------------------------------------------------------------------
  * Vector quantisation (SimpleVectorQuantizer.forward, models/bottleneck.py:262-324).
  *   mode 0: stochastic=False  argmin(|z|^2+|e|^2-2z.e)           (:282-290)

@@ -39,6 +39,8 @@ from .loss import TransformerDiscriminator, VQLPIPSWithDiscriminator  # noqa: F4
 from .fsq import FSQ  # noqa: F401
 from . import design  # noqa: F401
 from . import varlen  # noqa: F401
+from . import titok_model  # noqa: F401  (registers 'titok')
+from .titok_model import TiTok  # noqa: F401
 from .design import (AutoEncoder, CrossAttention, Encoder, FirstFrameEncoder, LearnedQueryTokens, RMSNorm, SelfAttention,  # noqa: F401
                      TransformerBlock, TransformerStack, UnifiedDecoder)
 

@@ -14,6 +14,10 @@ No CPU path: CPU tensors are refused by hip.ptr().
 The layers of the reference's `autoencoder_design` are here as well: CrossAttentionLayer, and the self-attention block of its stack
 (SelfAttentionLayer, FeedForwardLayer, ResidualScale with the learnable 0-dim residual scale read on the device, RMSNormF32 for the stack's
 fp32 final norm); design.py holds their parameters.
+
+The packed `titok` model's Functions are at the end: VarlenAttend / VarlenAttentionLayer (the layer of models/model_titok), its residual sibling
+and VarlenFeedForwardLayer (one Function per half block), and the data movement of csrc/vt_packed.hip (PatchRowsClips, UnpatchifyClips, PackedScatter,
+PackedGather); varlen.py and titok_model.py hold their parameters.
 """
 import ctypes
 import functools
@@ -795,3 +799,147 @@ class VarlenAttentionLayer(torch.autograd.Function):
         wg.run()
         dx, _, dg, db, _ = hip.layernorm_bwd(dxn, x2, pw, mean, rstd, want_dxsum=False, want_dxb=False)
         return _grads(ctx, VarlenAttentionLayer, x=dx, pre_w=dg, pre_b=db, to_qkv_w=dwqkv, q_w=dq_w, q_b=dq_b, k_w=dk_w, k_b=dk_b, out_proj_w=dwo)
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# the packed `titok` model (models/model_titok/base/blocks.py:82-222): clips of different sizes, [lead | tail] sequences, its blocks
+# ------------------------------------------------------------------------------------------------------------------------
+class PatchRowsClips(torch.autograd.Function):
+    """A list of fp32 clips [C, T_b, H_b, W_b] -> bf16 patch rows [sum_b G_b, C pt p p], clip after clip (the rearrange + cat of
+    blocks.py:128-129, rounded as the Linear that follows reads it under autocast): ONE vt_patchify_clips launch; backward = ONE
+    vt_unpatchify_clips launch.  (The clips are a variable argument list, so the gradients go back by position, as BlockStack's do.)"""
+
+    @staticmethod
+    def forward(ctx, pt, p, *clips):
+        clips = [v.contiguous().float() for v in clips]
+        ctx.geom = (pt, p, clips[0].shape[0] if clips else 0, [tuple(v.shape[1:]) for v in clips])
+        return hip.patchify_clips(clips, pt, p)
+
+    @staticmethod
+    def backward(ctx, drows):
+        pt, p, C, sizes = ctx.geom
+        dclips = hip.unpatchify_clips(drows.contiguous().float(), sizes, C, pt, p)
+        return (None, None, *[g if n else None for g, n in zip(dclips, ctx.needs_input_grad[2:])])
+
+
+class UnpatchifyClips(torch.autograd.Function):
+    """fp32 rows [sum_b G_b, C pt p p] in (c, dt, dy, dx) column order -> a tuple of fp32 clips [C, T_b, H_b, W_b], sizes = ((T_b, H_b, W_b), ...)
+    (the split + rearrange of blocks.py:212-220): ONE vt_unpatchify_clips launch; backward = ONE vt_patchify_clips launch over the list of
+    d clips (a clip without a gradient counts as zeros)."""
+
+    @staticmethod
+    def forward(ctx, rows, sizes, C, pt, p):
+        ctx.geom = (tuple(tuple(int(v) for v in s) for s in sizes), C, pt, p)
+        return tuple(hip.unpatchify_clips(rows.contiguous().float(), ctx.geom[0], C, pt, p))
+
+    @staticmethod
+    def backward(ctx, *dclips):
+        sizes, C, pt, p = ctx.geom
+        dev = next(g for g in dclips if g is not None).device
+        full = [g.contiguous().float() if g is not None else torch.zeros(C, *s, device=dev) for g, s in zip(dclips, sizes)]
+        return _grads(ctx, UnpatchifyClips, rows=hip.patchify_clips(full, pt, p).float())
+
+
+class PackedScatter(torch.autograd.Function):
+    """The packed residual stream fp32 [M, D] of blocks.py:132-135 / :197-200: sequence b = rows cu[b] .. cu[b+1]-1 = [lead[b] lead rows |
+    tail rows]; the `which` segments (hip.PACKED_LEAD / PACKED_TAIL) take the rows of the compact src, the other segments every row = vec
+    (mask_token [1, D]).  Backward: d src = PackedGather of the same segments, d vec = vt_packed_segment_colsum of the other ones."""
+
+    @staticmethod
+    def forward(ctx, src, vec, cu, lead, which):
+        ctx.geom = (hip.cu_seqlens_list(cu), [int(v) for v in lead], which, vec.shape)
+        return hip.packed_scatter(src.contiguous().float(), ctx.geom[0], ctx.geom[1], which, vec=vec.detach().contiguous().float())
+
+    @staticmethod
+    def backward(ctx, dout):
+        cu, lead, which, vshape = ctx.geom
+        need = _needs(ctx, PackedScatter)
+        d = dout.contiguous().float()
+        dsrc = hip.packed_gather(d, cu, lead, which) if need["src"] else None
+        dvec = hip.packed_segment_colsum(d, cu, lead, 1 - which).reshape(vshape) if need["vec"] else None
+        return _grads(ctx, PackedScatter, src=dsrc, vec=dvec)
+
+
+class PackedGather(torch.autograd.Function):
+    """The `which` segments' rows of a packed fp32 [M, D], compact (blocks.py:140-142: the latent rows; :207-209: the grid rows).
+    Backward: PackedScatter with zeros in the other segments."""
+
+    @staticmethod
+    def forward(ctx, packed, cu, lead, which):
+        ctx.geom = (hip.cu_seqlens_list(cu), [int(v) for v in lead], which)
+        return hip.packed_gather(packed.contiguous().float(), *ctx.geom)
+
+    @staticmethod
+    def backward(ctx, dout):
+        cu, lead, which = ctx.geom
+        return _grads(ctx, PackedGather, packed=hip.packed_scatter(dout.contiguous().float(), cu, lead, which))
+
+
+class VarlenAttentionResidualLayer(torch.autograd.Function):
+    """x + Attn(x) (models/model_titok/base/transformer.py:83): VarlenAttentionLayer's five launches with the residual in the out_proj GEMM's
+    epilogue, which rounds the product to bf16 first and adds the fp32 x second -- bit for bit x + VarlenAttentionLayer(x).  Same arguments in
+    the same order, so the backward IS VarlenAttentionLayer's (it reads ctx only), plus dout on the residual path."""
+
+    @staticmethod
+    def forward(ctx, x, cos, sin, cu, pre_w, pre_b, to_qkv_w, q_w, q_b, k_w, k_b, out_proj_w, Hq, Hkv, eps, pk_qkv, pk_o):
+        hip.require_gpu(x, cos, sin, pre_w, pre_b, to_qkv_w, q_w, q_b, k_w, k_b, out_proj_w)
+        M, D = x.shape
+        G = 64 * Hkv
+        assert D == 64 * Hq and to_qkv_w.shape == (D + 2 * G, D) and cos.shape == (M, 32) == sin.shape
+        x2 = x.contiguous().float()
+        pw, pb, qw, qb, kw, kb = (t.detach().float().contiguous() for t in (pre_w, pre_b, q_w, q_b, k_w, k_b))
+        cos, sin = cos.contiguous(), sin.contiguous()
+        xn, mean, rstd = hip.layernorm_fwd(x2, pw, pb, eps)
+        qkv = hip.gemm_nt(xn, pk_qkv[0], hip.EPI_BF16)
+        qkr = hip.qknorm_rope_gqa_fwd(qkv, Hq, Hkv, qw, qb, kw, kb, eps, cos, sin)
+        o, lse2 = hip.attention_varlen_fwd(qkr[:, :D], qkr[:, D:D + G], qkr[:, D + G:], cu, Hq, Hkv)
+        out = hip.gemm_nt(o, pk_o[0], hip.EPI_F32, residual=x2, round_bf16=True)
+        ctx.save_for_backward(x2, pw, qw, kw, cos, sin, mean, rstd, xn, qkv, qkr, o, lse2, pk_qkv[1], pk_o[1])
+        ctx.geom = (list(cu), Hq, Hkv, eps)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        grads = VarlenAttentionLayer.backward(ctx, dout)
+        return (grads[0] + dout if grads[0] is not None else None, *grads[1:])
+
+
+class VarlenFeedForwardLayer(torch.autograd.Function):
+    """ffd(x) of models/model_titok/base/transformer.py:20-30 on x fp32 [M, D], and with residual=True x + ffd(x) (:84): LayerNorm(x); the first
+    Linear (N = 2 inner, columns x | gate); vt_geglu_fwd into an operand whose row stride is padded to a multiple of 64 (inner is 352 at width
+    128, 1376 at 512); the second Linear, whose epilogue rounds to bf16 first and adds the fp32 x second -- bit for bit x + ffd(x).  No gate and
+    no stream rescale.  pk_1: operand copies of the first Linear; pk_2: of the second with the contraction dim padded (packs.get(k_pad=))."""
+
+    @staticmethod
+    def forward(ctx, x, ln_w, ln_b, fc1_w, fc2_w, eps, residual, pk_1, pk_2):
+        hip.require_gpu(x, ln_w, ln_b, fc1_w, fc2_w)
+        M, D = x.shape
+        inner = fc2_w.shape[1]
+        assert fc1_w.shape == (2 * inner, D) and fc2_w.shape[0] == D
+        x2 = x.contiguous().float()
+        w, b = ln_w.detach().float().contiguous(), ln_b.detach().float().contiguous()
+        xn, mean, rstd = hip.layernorm_fwd(x2, w, b, eps)
+        h = hip.gemm_nt(xn, pk_1[0], hip.EPI_BF16)                      # [M, 2 inner] = [x | gate]
+        a = hip.geglu_fwd(h, lda=_pad64(inner))
+        out = hip.gemm_nt(a, pk_2[0], hip.EPI_F32, residual=x2 if residual else None, round_bf16=True)
+        ctx.save_for_backward(x2, w, mean, rstd, xn, h, a, pk_1[1], pk_2[1])
+        ctx.geom = (inner, residual)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x2, w, mean, rstd, xn, h, a, w1_t, w2_t = ctx.saved_tensors
+        inner, residual = ctx.geom
+        need = _needs(ctx, VarlenFeedForwardLayer)
+        d2 = dout.contiguous().float()
+        gb = hip.cast_rows(d2)
+        da = hip.gemm_nt(gb, w2_t, hip.EPI_BF16)                        # [M, pad64(inner)]
+        dh = hip.geglu_bwd(da, h)
+        dxn = hip.gemm_nt(dh, w1_t, hip.EPI_BF16)
+        wg = _WeightGrads()
+        dw1 = wg.add(dh, xn, need["fc1_w"])
+        dw2p = wg.add(gb, a, need["fc2_w"])                             # [D, pad64(inner)]
+        wg.run()
+        dw2 = dw2p[:, :inner].contiguous() if need["fc2_w"] else None
+        dx, _, dg, db, _ = hip.layernorm_bwd(dxn, x2, w, mean, rstd, dres=d2 if residual else None, want_dxsum=False, want_dxb=False)
+        return _grads(ctx, VarlenFeedForwardLayer, x=dx, ln_w=dg, ln_b=db, fc1_w=dw1, fc2_w=dw2)

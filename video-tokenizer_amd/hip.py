@@ -35,6 +35,11 @@ class GemmTN(ctypes.Structure):
     _fields_ = [("A", c_vp), ("lda", c_i64), ("B", c_vp), ("ldb", c_i64), ("M", c_i32), ("P", c_i32), ("Q", c_i32),
                 ("out", c_vp), ("ldo", c_i64), ("p_lim", c_i32), ("q_lim", c_i32), ("row_perm", c_vp), ("tile", c_i32)]
 
+class Clip(ctypes.Structure):
+    """vtClip: one clip of vt_patchify_clips / vt_unpatchify_clips, a contiguous fp32 [C, T, H, W] on the device"""
+    _fields_ = [("data", c_vp), ("T", c_i32), ("H", c_i32), ("W", c_i32)]
+
+
 # Tile generation the gemm_nt / gemm_tn_grouped wrappers below put into vtGemmNT.tile / vtGemmTN.tile when the caller
 # passes none: 0 = the library's automatic choice.  Tests and tools set it to A/B the tile generations; it lives on the
 # Python side only (the C library has no setting of its own, the field travels with every call).
@@ -74,6 +79,12 @@ SIGNATURES = {
                                         c_vp]),
     "vt_attention_varlen_bwd": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, ctypes.POINTER(c_i32), c_i32, c_i32, c_i32, c_i32,
                                         c_i32, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp]),
+    "vt_patchify_clips": (c_i32, [ctypes.POINTER(Clip), c_i32, c_i32, c_i32, c_i32, c_vp, c_i64, c_vp]),
+    "vt_unpatchify_clips": (c_i32, [c_vp, c_i64, ctypes.POINTER(Clip), c_i32, c_i32, c_i32, c_i32, c_vp]),
+    "vt_packed_scatter": (c_i32, [c_vp, c_vp, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32), c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    "vt_packed_gather": (c_i32, [c_vp, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32), c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    "vt_packed_segment_colsum_workspace_bytes": (c_sz, [c_i32]),
+    "vt_packed_segment_colsum": (c_i32, [c_vp, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32), c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "vt_vq_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32]),
     "vt_vq_forward": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_f32, c_f32, c_f32, c_u64, c_vp, c_vp,
                               c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
@@ -590,6 +601,107 @@ def attention_varlen_bwd(q, k, v, o, dO, lse2, cu_seqlens, Hq, Hkv, hd=64, dq=No
                                         cu, n, M, Hq, Hkv, hd, ptr(dq), _rows_view(dq, "dq"), ptr(dk), _rows_view(dk, "dk"), ptr(dv),
                                         _rows_view(dv, "dv"), ptr(delta), stream()), "vt_attention_varlen_bwd")
     return dq, dk, dv
+
+
+# ---- data movement of the packed titok model (csrc/vt_packed.hip) ----
+PACKED_LEAD, PACKED_TAIL = 0, 1      # VT_PACKED_LEAD / VT_PACKED_TAIL: which segment of every [lead | tail] sequence a call works on
+
+
+def _clip_table(clips, C):
+    """the vtClip host array of a list of fp32 [C, T, H, W] device tensors (the library validates sizes and alignment)"""
+    require_gpu(*clips)
+    for v in clips:
+        if v.dim() != 4 or v.shape[0] != C or v.dtype != torch.float32 or not v.is_contiguous():
+            raise HipError(f"clips: expected contiguous fp32 [{C}, T, H, W] tensors, got {v.dtype} {tuple(v.shape)} strides {tuple(v.stride())}")
+    arr = (Clip * max(len(clips), 1))()
+    for a, v in zip(arr, clips):
+        a.data, a.T, a.H, a.W = v.data_ptr(), v.shape[1], v.shape[2], v.shape[3]
+    return arr
+
+
+def clip_grids(sizes, pt, p):
+    """token grids [(T / pt, H / p, W / p)] of clips of the given (T, H, W)"""
+    return [(int(T) // pt, int(H) // p, int(W) // p) for T, H, W in sizes]
+
+
+def patchify_clips(clips, pt, p, out=None):
+    """a list of fp32 [C, T_b, H_b, W_b] clips -> bf16 patch rows [sum_b G_b, C * pt * p * p], clip after clip, in ONE launch; columns
+    (c, dt, dy, dx), tokens (t, h, w): per clip the rearrange of the reference's TiTokEncoder.forward"""
+    C = clips[0].shape[0] if len(clips) else 0
+    arr = _clip_table(clips, C)
+    G = sum(t * h * w for t, h, w in clip_grids([v.shape[1:] for v in clips], pt, p))
+    rows = torch.empty(G, C * pt * p * p, device=clips[0].device if len(clips) else None, dtype=torch.bfloat16) if out is None else out
+    if out is not None and (out.dtype != torch.bfloat16 or tuple(out.shape) != (G, C * pt * p * p) or not out.is_contiguous() or not out.is_cuda):
+        raise HipError(f"patchify_clips: out must be a contiguous bf16 device matrix [{G}, {C * pt * p * p}], got {out.dtype} {tuple(out.shape)}")
+    check(lib().vt_patchify_clips(arr, len(clips), C, pt, p, ptr(rows), G, stream()), "vt_patchify_clips")
+    return rows
+
+
+def unpatchify_clips(rows, sizes, C, pt, p, out=None):
+    """fp32 rows [sum_b G_b, C * pt * p * p] -> a list of fp32 [C, T_b, H_b, W_b] clips, sizes = [(T_b, H_b, W_b)], in ONE launch"""
+    require_gpu(rows)
+    if rows.dtype != torch.float32 or rows.dim() != 2 or not rows.is_contiguous() or rows.shape[1] != C * pt * p * p:
+        raise HipError(f"unpatchify_clips: expected contiguous fp32 rows [*, {C * pt * p * p}], got {rows.dtype} {tuple(rows.shape)}")
+    clips = [torch.empty(C, int(T), int(H), int(W), device=rows.device, dtype=torch.float32) for T, H, W in sizes] if out is None else out
+    check(lib().vt_unpatchify_clips(ptr(rows), rows.shape[0], _clip_table(clips, C), len(clips), C, pt, p, stream()), "vt_unpatchify_clips")
+    return clips
+
+
+def _packed_tables(cu_seqlens, lead):
+    cu, n, M = cu_seqlens_host(cu_seqlens)
+    ld = cu_seqlens_list([0] + list(lead))[1:]           # the one conversion: floats are refused, not truncated
+    if len(ld) != n:
+        raise HipError(f"packed rows: {len(ld)} lead counts for {n} sequences")
+    return cu, (c_i32 * max(n, 1))(*ld), n, M, ld
+
+
+def _segment_rows(cu, ld, n, which):
+    return sum(ld) if which == PACKED_LEAD else cu[n] - sum(ld)
+
+
+def _f32_rows(t, what, rows=None):
+    if t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous() or (rows is not None and t.shape[0] != rows):
+        raise HipError(f"{what}: expected a contiguous fp32 matrix" + (f" of {rows} rows" if rows is not None else "") + f", got {t.dtype} {tuple(t.shape)}")
+    return t.shape[1]
+
+
+def packed_scatter(src, cu_seqlens, lead, which, vec=None, out=None):
+    """dst fp32 [M, D]: sequence b = rows cu[b] .. cu[b+1]-1 = [lead[b] lead rows | tail rows]; the `which` segments take the rows of the
+    compact src in order, the other segments vec [D] (zeros when None)"""
+    require_gpu(src, vec, out)
+    cu, ld, n, M, lst = _packed_tables(cu_seqlens, lead)
+    D = _f32_rows(src, "packed_scatter: src", _segment_rows(cu, lst, n, which) if which in (PACKED_LEAD, PACKED_TAIL) else None)
+    if vec is not None and (vec.dtype != torch.float32 or vec.numel() != D or not vec.is_contiguous()):
+        raise HipError(f"packed_scatter: vec must be contiguous fp32 with {D} elements, got {vec.dtype} {tuple(vec.shape)}")
+    out = torch.empty(M, D, device=src.device, dtype=torch.float32) if out is None else out
+    if _f32_rows(out, "packed_scatter: out", M) != D:
+        raise HipError(f"packed_scatter: out has {out.shape[1]} columns, src has {D}")
+    check(lib().vt_packed_scatter(ptr(src), ptr(vec), cu, ld, n, M, D, which, ptr(out), stream()), "vt_packed_scatter")
+    return out
+
+
+def packed_gather(packed, cu_seqlens, lead, which, out=None):
+    """the `which` segments' rows of a packed fp32 [M, D], in order -> compact fp32 [sum_b |segment_b|, D]"""
+    require_gpu(packed, out)
+    cu, ld, n, M, lst = _packed_tables(cu_seqlens, lead)
+    D = _f32_rows(packed, "packed_gather: packed", M)
+    R = max(_segment_rows(cu, lst, n, which), 0) if which in (PACKED_LEAD, PACKED_TAIL) else 0
+    out = torch.empty(R, D, device=packed.device, dtype=torch.float32) if out is None else out
+    if _f32_rows(out, "packed_gather: out", R) != D:
+        raise HipError(f"packed_gather: out has {out.shape[1]} columns, packed has {D}")
+    check(lib().vt_packed_gather(ptr(packed), cu, ld, n, M, D, which, ptr(out), stream()), "vt_packed_gather")
+    return out
+
+
+def packed_segment_colsum(packed, cu_seqlens, lead, which):
+    """out fp32 [D] = the sum of every row of the `which` segments of a packed fp32 [M, D], in a fixed order, read in place"""
+    require_gpu(packed)
+    cu, ld, n, M, _ = _packed_tables(cu_seqlens, lead)
+    D = _f32_rows(packed, "packed_segment_colsum: packed", M)
+    out = torch.empty(D, device=packed.device, dtype=torch.float32)
+    ws = _ws(lib().vt_packed_segment_colsum_workspace_bytes(D), packed.device)
+    check(lib().vt_packed_segment_colsum(ptr(packed), cu, ld, n, M, D, which, ptr(out), ptr(ws), stream()), "vt_packed_segment_colsum")
+    return out
 
 
 def _gqa_tables_ok(cos, sin, M):

@@ -1,7 +1,7 @@
 """Packed variable-length attention layer of the reference's `titok` family (models/model_titok/base/transformer.py:32-62, base/rope.py,
 base/blocks.py:32-64): the clips of a batch have different sizes, so they are packed into one [sum L_b, D] tensor and every sequence attends
-inside itself; the layers are grouped-query (Hq query heads over Hkv KV heads).  This module is the layer and its rotary tables; the
-encoder, the decoder and the `titok` registry entry build on it.
+inside itself; the layers are grouped-query (Hq query heads over Hkv KV heads).  This module is the layer and its rotary tables, and below
+them the feed-forward, the block stack, TiTokEncoder and TiTokDecoder (base/blocks.py:67-222); titok_model.py holds the `titok` registry entry.
 """
 import math
 
@@ -103,3 +103,197 @@ class Attn(nn.Module):
         return F_.VarlenAttentionLayer.apply(x, cos, sin, cu, self.pre_ln.weight, self.pre_ln.bias, self.to_qkv.weight, self.q_norm.weight,
                                              self.q_norm.bias, self.k_norm.weight, self.k_norm.bias, self.out_proj.weight, self.q_heads,
                                              self.kv_heads, self.pre_ln.eps, packs.get(self, ("to_qkv",)), packs.get(self, ("out_proj",)))
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# the model around the layer: feed-forward, block stack, encoder and decoder (transformer.py:14-30, 65-85; blocks.py:67-222)
+# ------------------------------------------------------------------------------------------------------------------------
+MAX_CLIPS = hip.VARLEN_MAX_SEQ                   # clips per call: one table entry each in the kernels' arguments
+_TABLE_CACHE_ENTRIES = 8
+
+
+class GEGLU(nn.Module):
+    """transformer.py:14-17, parameterless: index 2 of ffd.  It never runs on its own here: FeedForward.forward is one Function."""
+
+    def forward(self, x):
+        raise RuntimeError("varlen.GEGLU is a placeholder at the reference's index: call the surrounding varlen.ffd(...) module, which runs as one Function")
+
+
+class FeedForward(nn.Sequential):
+    """the nn.Sequential of transformer.py:20-30 (LayerNorm at 0, Linear at 1, GEGLU at 2, Dropout(0.) at 3, Linear at 4; state-dict keys
+    0.weight / 0.bias / 1.weight / 4.weight) whose forward is functional.VarlenFeedForwardLayer on x fp32 [M, D]"""
+
+    def forward(self, x, residual=False):
+        hip.require_gpu(x, *self.parameters())
+        inner = self[4].in_features
+        return F_.VarlenFeedForwardLayer.apply(x, self[0].weight, self[0].bias, self[1].weight, self[4].weight, self[0].eps, residual,
+                                               packs.get(self, ("1",)), packs.get(self, ("4",), k_pad=(inner + 63) // 64 * 64))
+
+
+def ffd(dim, mult=4, mult_of=32, dropout=0.):
+    if dim not in LN_WIDTHS:
+        raise ValueError(f"varlen.ffd: dim {dim} must be a LayerNorm width {LN_WIDTHS}")
+    if dropout:
+        raise ValueError("varlen.ffd: dropout is not built (the reference runs its layers with 0.)")
+    inner_dim = int(mult * (2 / 3) * dim)
+    inner_dim = mult_of * ((inner_dim + mult_of - 1) // mult_of)
+    return FeedForward(nn.LayerNorm(dim), nn.Linear(dim, inner_dim * 2, bias=False), GEGLU(), nn.Dropout(dropout), nn.Linear(inner_dim, dim, bias=False))
+
+
+class ResidualAttentionBlock(nn.Module):
+    """transformer.py:65-85: num_layer x {x = x + Attn(x); x = x + ffd(x)} on the packed x fp32 [M, D]; keys attn_layer.{i}.*, ffd_layer.{i}.*.
+    One Function per half block, the residual additions in the epilogues of the out_proj / second feed-forward GEMMs.  cu_seqlens is turned
+    into a host list once and shared by all layers (a device tensor costs one synchronisation)."""
+
+    def __init__(self, embed_dim=512, heads=(8, 2), mlp_ratio=4, num_layer=2):
+        super().__init__()
+        self.num_layer = num_layer
+        self.attn_layer = nn.Sequential()
+        self.ffd_layer = nn.Sequential()
+        for _ in range(num_layer):
+            self.attn_layer.append(Attn(embed_dim, list(heads)))
+            self.ffd_layer.append(ffd(embed_dim, mlp_ratio))
+
+    def forward(self, x, freqs, cu_seqlens, max_seqlen=None):
+        cu = hip.cu_seqlens_list(cu_seqlens)
+        hip.require_gpu(x, *self.parameters())
+        if isinstance(freqs, (tuple, list)):
+            cos, sin = freqs
+        else:
+            cos, sin = freqs.real.float().contiguous().to(x.device), freqs.imag.float().contiguous().to(x.device)
+        for a, f in zip(self.attn_layer, self.ffd_layer):
+            x = F_.VarlenAttentionResidualLayer.apply(x, cos, sin, cu, a.pre_ln.weight, a.pre_ln.bias, a.to_qkv.weight, a.q_norm.weight, a.q_norm.bias,
+                                                      a.k_norm.weight, a.k_norm.bias, a.out_proj.weight, a.q_heads, a.kv_heads, a.pre_ln.eps,
+                                                      packs.get(a, ("to_qkv",)), packs.get(a, ("out_proj",)))
+            x = f(x, residual=True)
+        return x
+
+
+def init_weights(module):
+    """blocks.py:67-79"""
+    if isinstance(module, nn.Linear):
+        module.weight.data = nn.init.trunc_normal_(module.weight.data, mean=0.0, std=0.02)
+        if module.bias is not None:
+            nn.init.constant_(module.bias, 0)
+    elif isinstance(module, nn.LayerNorm):
+        if module.bias is not None:
+            nn.init.constant_(module.bias, 0)
+        if module.weight is not None:
+            nn.init.constant_(module.weight, 1.0)
+    elif isinstance(module, (nn.Conv3d, nn.Conv2d)):
+        nn.init.xavier_uniform_(module.weight)
+        nn.init.zeros_(module.bias)
+
+
+class _PackedSide(nn.Module):
+    """What TiTokEncoder and TiTokDecoder share: the geometry of a call -- grids, boundaries and lead counts as host lists, built once per
+    forward and never read back from the device -- and a small cache of the rotary tables keyed by (grids, token_counts), so that a steady
+    training loop does not rebuild float64 tables every step.  `RoPE` of the reference holds no parameter or persistent buffer: no key."""
+
+    def _setup(self, model_size, patch_size, dims):
+        self.patch_size = tuple(int(v) for v in patch_size)
+        self.width, self.num_layers, self.heads, mlp_ratio = dims if dims is not None else get_model_dims(model_size)
+        if self.width != 64 * self.heads[0]:
+            raise ValueError(f"{type(self).__name__}: width {self.width} must be 64 * q heads ({self.heads[0]}): head dimension 64 only")
+        if self.width not in LN_WIDTHS:
+            raise ValueError(f"{type(self).__name__}: width {self.width} must be a LayerNorm width {LN_WIDTHS}")
+        if self.patch_size[1] != self.patch_size[2] or self.patch_size[1] % 8:
+            raise ValueError(f"{type(self).__name__}: patch_size {self.patch_size} must be (pt, p, p) with p a multiple of 8")
+        self._tables = {}
+        return mlp_ratio
+
+    def geometry(self, sizes, token_counts):
+        """sizes: (T, H, W) per clip -> (grids, grid_sizes, seq_lens, cu); refuses what the kernels would"""
+        who = type(self).__name__
+        counts = [int(n) for n in token_counts]
+        if not 1 <= len(sizes) <= MAX_CLIPS:
+            raise ValueError(f"{who}: {len(sizes)} clips in one call; 1..{MAX_CLIPS} are supported")
+        if len(counts) != len(sizes):
+            raise ValueError(f"{who}: {len(counts)} token counts for {len(sizes)} clips")
+        if any(n < 1 for n in counts):
+            raise ValueError(f"{who}: every clip needs at least one latent token, got {counts}")
+        for s in sizes:
+            if len(s) != 3 or any(int(d) <= 0 or int(d) % q for d, q in zip(s, self.patch_size)):
+                raise ValueError(f"{who}: a clip of size {tuple(s)} (T, H, W) is no positive multiple of the patch {self.patch_size}")
+        grids = [tuple(int(d) // q for d, q in zip(s, self.patch_size)) for s in sizes]
+        grid_sizes = [math.prod(g) for g in grids]
+        seq_lens = [g + n for g, n in zip(grid_sizes, counts)]
+        cu = [0]
+        for n in seq_lens:
+            cu.append(cu[-1] + n)
+        return grids, grid_sizes, seq_lens, cu
+
+    def rope_tables(self, grids, token_counts, device):
+        """(cos, sin) fp32 [M, 32] on `device` from rope_freqs, cached on the module by (grids, token_counts, device)"""
+        key = (tuple(tuple(g) for g in grids), tuple(int(n) for n in token_counts), str(device))
+        hit = self._tables.get(key)
+        if hit is None:
+            while len(self._tables) >= _TABLE_CACHE_ENTRIES:
+                self._tables.pop(next(iter(self._tables)))
+            _, cos, sin = rope_freqs(grids, token_counts, device)
+            hit = self._tables[key] = (cos, sin)
+        return hit
+
+
+class TiTokEncoder(_PackedSide):
+    """blocks.py:82-147.  forward(x, token_counts): x a list of clips [in_channels, T_b, H_b, W_b] of any sizes that the patch divides,
+    token_counts[b] >= 1 latent tokens for clip b -> the packed latents fp32 [sum token_counts, out_channels].  Launches around the layer
+    stack: vt_patchify_clips, the proj_in GEMM, vt_packed_scatter ([mask_token x n_b | patch rows]), vt_packed_gather (the latent rows),
+    ln_post, the proj_out GEMM.  `_dims` = (width, layers, [Hq, Hkv], mlp_ratio) overrides model_size for small tests."""
+
+    def __init__(self, model_size="tiny", patch_size=(4, 8, 8), in_channels=3, out_channels=5, max_grid=(32, 256, 256), max_tokens=2048, _dims=None):
+        super().__init__()
+        mlp_ratio = self._setup(model_size, patch_size, _dims)
+        self.token_size, self.in_channels = out_channels, in_channels
+        self.mask_token = nn.Parameter(self.width ** -0.5 * torch.randn(1, self.width))
+        self.proj_in = nn.Linear(in_channels * math.prod(self.patch_size), self.width)
+        self.model_layers = ResidualAttentionBlock(embed_dim=self.width, heads=self.heads, mlp_ratio=mlp_ratio, num_layer=self.num_layers)
+        self.ln_post = nn.LayerNorm(self.width)
+        self.proj_out = nn.Linear(self.width, self.token_size, bias=True)
+
+    def forward(self, x, token_counts):
+        x = list(x)
+        hip.require_gpu(*x, *self.parameters())
+        if any(v.dim() != 4 or v.shape[0] != self.in_channels for v in x):
+            raise ValueError(f"TiTokEncoder: every clip must be [{self.in_channels}, T, H, W], got {[tuple(v.shape) for v in x]}")
+        grids, _, seq_lens, cu = self.geometry([v.shape[1:] for v in x], token_counts)
+        counts = [int(n) for n in token_counts]
+        rows = F_.PatchRowsClips.apply(self.patch_size[0], self.patch_size[1], *x)
+        tok = F_.Linear.apply(rows, self.proj_in.weight, self.proj_in.bias)
+        h = F_.PackedScatter.apply(tok, self.mask_token, cu, counts, hip.PACKED_TAIL)
+        h = self.model_layers(h, self.rope_tables(grids, counts, h.device), cu, max(seq_lens))
+        lat = F_.PackedGather.apply(h, cu, counts, hip.PACKED_LEAD)
+        lat = F_.LayerNormRows.apply(lat, self.ln_post.weight, self.ln_post.bias, self.ln_post.eps)
+        return F_.Linear.apply(lat, self.proj_out.weight, self.proj_out.bias)
+
+
+class TiTokDecoder(_PackedSide):
+    """blocks.py:150-222.  forward(x, token_counts, grids): x the packed codes [sum token_counts, in_channels], grids[b] = (T_b, H_b, W_b) of
+    clip b in PIXELS (the reference's argument) -> a list of clips fp32 [out_channels, T_b, H_b, W_b].  Launches around the layer stack: the
+    proj_in GEMM, vt_packed_scatter ([code rows | mask_token x G_b]), ln_pre, vt_packed_gather (the grid rows), the proj_out GEMM,
+    vt_unpatchify_clips.  ln_pre's output is rounded to bf16 (the LayerNorm kernel's output format), where autocast keeps fp32."""
+
+    def __init__(self, model_size="tiny", patch_size=(4, 8, 8), in_channels=5, out_channels=3, max_grid=(32, 256, 256), max_tokens=2048, _dims=None):
+        super().__init__()
+        mlp_ratio = self._setup(model_size, patch_size, _dims)
+        self.token_size, self.out_channels = in_channels, out_channels
+        self.mask_token = nn.Parameter(self.width ** -0.5 * torch.randn(1, self.width))
+        self.proj_in = nn.Linear(self.token_size, self.width, bias=True)
+        self.ln_pre = nn.LayerNorm(self.width)
+        self.model_layers = ResidualAttentionBlock(embed_dim=self.width, heads=self.heads, mlp_ratio=mlp_ratio, num_layer=self.num_layers)
+        self.proj_out = nn.Linear(self.width, out_channels * math.prod(self.patch_size))
+
+    def forward(self, x, token_counts, grids):
+        hip.require_gpu(x, *self.parameters())
+        sizes = [tuple(int(d) for d in g) for g in grids]
+        tgrids, _, seq_lens, cu = self.geometry(sizes, token_counts)
+        counts = [int(n) for n in token_counts]
+        if x.dim() != 2 or tuple(x.shape) != (sum(counts), self.token_size):
+            raise ValueError(f"TiTokDecoder: expected packed codes [{sum(counts)}, {self.token_size}], got {tuple(x.shape)}")
+        tok = F_.Linear.apply(x, self.proj_in.weight, self.proj_in.bias)
+        h = F_.PackedScatter.apply(tok, self.mask_token, cu, counts, hip.PACKED_LEAD)
+        h = F_.LayerNormRows.apply(h, self.ln_pre.weight, self.ln_pre.bias, self.ln_pre.eps)
+        h = self.model_layers(h, self.rope_tables(tgrids, counts, h.device), cu, max(seq_lens))
+        rows = F_.PackedGather.apply(h, cu, counts, hip.PACKED_TAIL)
+        rows = F_.Linear.apply(rows, self.proj_out.weight, self.proj_out.bias)
+        return list(F_.UnpatchifyClips.apply(rows, sizes, self.out_channels, self.patch_size[0], self.patch_size[1]))
