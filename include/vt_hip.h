@@ -195,6 +195,22 @@ int vt_unpatchify(const float* rows, int32_t B, int32_t C, int32_t T, int32_t S,
                   vtStream stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Two-segment patchify / unpatchify (csrc/vt_dualpatch.hip): the ends of `autoencoder_dualpatch`.  Its encoder cuts the clip along time,
+ * x[:, :, :pt_first] into Conv3d(kernel = stride = (pt_first, ph, pw)) and x[:, :, pt_first:] into Conv3d((pt_rest, ph, pw))
+ * (models/model_dualpatch/base/blocks.py:99-112); its decoder ends in two ConvTranspose3d whose outputs are concatenated along T
+ * (blocks.py:252-257).  video fp32 [B, C, T, H, W] contiguous; frames [0, T0) <-> rows0 [B (T0/pt0)(H/ph)(W/pw), C pt0 ph pw], frames
+ * [T0, T) <-> rows1 [B ((T-T0)/pt1)(H/ph)(W/pw), C pt1 ph pw]; token order (t, h, w) t-major per clip and column order (c, dt, dy, dx) as
+ * vt_patchify, and the same rounding to bf16.  vt_unpatchify_dual reads two fp32 row matrices and writes every element of video exactly
+ * once.  One launch each: no slice copy of the video, no torch.cat of the output.  H != W and ph != pw are fine.  Checked on the host
+ * before anything is launched (VT_ERR_INVALID, vt_last_error names the entry point and the offending value): pointers non-null and
+ * 16-byte aligned, every size > 0, 0 < T0 < T, T0 % pt0 == 0, (T - T0) % pt1 == 0, H % ph == 0, W % pw == 0, pw % 8 == 0.
+ * ------------------------------------------------------------------------------------------ */
+int vt_patchify_dual(const float* video, int32_t B, int32_t C, int32_t T, int32_t H, int32_t W, int32_t T0, int32_t pt0, int32_t pt1,
+                     int32_t ph, int32_t pw, void* rows0_bf16, void* rows1_bf16, vtStream stream);
+int vt_unpatchify_dual(const float* rows0, const float* rows1, int32_t B, int32_t C, int32_t T, int32_t H, int32_t W, int32_t T0, int32_t pt0,
+                       int32_t pt1, int32_t ph, int32_t pw, float* video, vtStream stream);
+
+/* ------------------------------------------------------------------------------------------
  * Fused attention, head_dim 64, no mask (timm Attention -> F.scaled_dot_product_attention inside
  * timm Block, models/transformer.py:52-59).  qkv bf16 [B,L,3,H,64]; o/dO bf16 [B,L,H,64];
  * lse2 fp32 [B,H,L] (log2-domain LSE of the scaled scores, saved for backward);

@@ -41,6 +41,8 @@ from . import design  # noqa: F401
 from . import varlen  # noqa: F401
 from . import titok_model  # noqa: F401  (registers 'titok')
 from .titok_model import TiTok  # noqa: F401
+from . import dualpatch  # noqa: F401  (registers 'autoencoder_dualpatch')
+from .dualpatch import AutoEncoderDualPatch, DualPatchDecoder, DualPatchEncoder  # noqa: F401
 from .design import (AutoEncoder, CrossAttention, Encoder, FirstFrameEncoder, LearnedQueryTokens, RMSNorm, SelfAttention,  # noqa: F401
                      TransformerBlock, TransformerStack, UnifiedDecoder)
 

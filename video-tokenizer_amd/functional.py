@@ -18,6 +18,9 @@ fp32 final norm); design.py holds their parameters.
 The packed `titok` model's Functions are at the end: VarlenAttend / VarlenAttentionLayer (the layer of models/model_titok), its residual sibling
 and VarlenFeedForwardLayer (one Function per half block), and the data movement of csrc/vt_packed.hip (PatchRowsClips, UnpatchifyClips, PackedScatter,
 PackedGather); varlen.py and titok_model.py hold their parameters.
+
+Last come the ends of `autoencoder_dualpatch` (DualPatchEmbed, DualConvTransposePatch, DualDecoderStream: a clip cut along time into two segments
+with a patch size each, csrc/vt_dualpatch.hip); dualpatch.py holds their parameters.
 """
 import ctypes
 import functools
@@ -943,3 +946,162 @@ class VarlenFeedForwardLayer(torch.autograd.Function):
         dw2 = dw2p[:, :inner].contiguous() if need["fc2_w"] else None
         dx, _, dg, db, _ = hip.layernorm_bwd(dxn, x2, w, mean, rstd, dres=d2 if residual else None, want_dxsum=False, want_dxb=False)
         return _grads(ctx, VarlenFeedForwardLayer, x=dx, ln_w=dg, ln_b=db, fc1_w=dw1, fc2_w=dw2)
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# `autoencoder_dualpatch` (models/model_dualpatch/base/blocks.py:12-258): a clip cut along time into two segments with a patch size each
+# ------------------------------------------------------------------------------------------------------------------------
+def _dual_maps(lead, n0, n1, L):
+    """the row maps of the two patch segments in a [B, L, D] stream [lead rows | n0 first-segment rows | n1 rest rows]"""
+    return hip.RowMap(n0, L, lead), hip.RowMap(n1, L, lead + n0)
+
+
+class DualPatchEmbed(torch.autograd.Function):
+    """Encoder.forward up to the layer stack (blocks.py:99-120): frames [0, T0) through Conv3d(kernel = stride = (pt0, ph, pw)) + pos0, frames
+    [T0, T) through Conv3d((pt1, ph, pw)) + pos1, behind `lead` rows of lead_table (latent_queries, broadcast over the batch) -> the residual
+    stream fp32 [B, lead + N0 + N1, D].  ONE vt_patchify_dual, two GEMMs whose epilogues round the conv output to bf16, add the fp32 position
+    table and write their rows into the stream through an output row map, ONE vt_assemble_rows for the lead rows: no slice copy of the video and
+    no torch.cat.  w0 [D, C, pt0, ph, pw], w1 [D, C, pt1, ph, pw], pos0 [1, N0, D], pos1 [1, N1, D], lead_table [1, lead, D]; T0 follows from N0.
+    Backward: vt_cast_rows per segment through the same maps, both weight gradients in one grouped launch, vt_colsum for the biases,
+    vt_batch_sum through a map for the three tables, and for d video two input-gradient GEMMs + ONE vt_unpatchify_dual."""
+
+    @staticmethod
+    def forward(ctx, video, w0, b0, pos0, w1, b1, pos1, lead, lead_table):
+        hip.require_gpu(video, w0, b0, pos0, w1, b1, pos1, lead_table)
+        D, C, pt0, ph, pw = w0.shape
+        pt1 = w1.shape[2]
+        B, _, T, H, W = video.shape
+        assert video.shape[1] == C and w1.shape == (D, C, pt1, ph, pw) and H % ph == 0 and W % pw == 0
+        n0 = pos0.numel() // D
+        T0 = n0 // ((H // ph) * (W // pw)) * pt0
+        n1 = hip.dual_grids(T, H, W, T0, pt0, pt1, ph, pw)[1]
+        assert hip.dual_grids(T, H, W, T0, pt0, pt1, ph, pw)[0] == n0 and pos1.numel() == n1 * D and lead_table.numel() == lead * D
+        L = lead + n0 + n1
+        video = video.contiguous().float()
+        rows0, rows1 = hip.patchify_dual(video, T0, pt0, pt1, ph, pw)          # bf16, (c, dt, dy, dx) inside a patch
+        (wb0, wt0), (wb1, wt1) = hip.pack_weight(w0), hip.pack_weight(w1)
+        out = torch.empty(B, L, D, device=video.device)
+        o2 = out.view(B * L, D)
+        m0, m1 = _dual_maps(lead, n0, n1, L)
+        hip.gemm_nt(rows0, wb0, hip.EPI_F32, bias=b0.detach().float().contiguous(), round_bf16=True, rowmod=pos0.detach().reshape(n0, D).float().contiguous(),
+                    rowmod_period=n0, omap=m0, out=o2)
+        hip.gemm_nt(rows1, wb1, hip.EPI_F32, bias=b1.detach().float().contiguous(), round_bf16=True, rowmod=pos1.detach().reshape(n1, D).float().contiguous(),
+                    rowmod_period=n1, omap=m1, out=o2)
+        hip.assemble_rows(o2, L, 0, B, lead, table=lead_table.detach().reshape(lead, D).float().contiguous())
+        ctx.save_for_backward(rows0, rows1, wt0, wt1)
+        ctx.geom = (B, C, T, H, W, T0, pt0, pt1, ph, pw, D, lead, n0, n1)
+        ctx.shapes = (w0.shape, w1.shape, pos0.shape, pos1.shape, lead_table.shape)
+        return out
+
+    @staticmethod
+    def backward(ctx, dtok):
+        rows0, rows1, wt0, wt1 = ctx.saved_tensors
+        B, C, T, H, W, T0, pt0, pt1, ph, pw, D, lead, n0, n1 = ctx.geom
+        L = lead + n0 + n1
+        need = _needs(ctx, DualPatchEmbed)
+        d2 = dtok.contiguous().float().view(B * L, D)
+        m0, m1 = _dual_maps(lead, n0, n1, L)
+        dT0 = hip.cast_rows(d2, rows=B * n0, rmap=m0)                          # the conv outputs are bf16 under autocast: so are their gradients
+        dT1 = hip.cast_rows(d2, rows=B * n1, rmap=m1)
+        dvideo = None
+        if need["video"]:
+            dvideo = hip.unpatchify_dual(hip.gemm_nt(dT0, wt0, hip.EPI_F32), hip.gemm_nt(dT1, wt1, hip.EPI_F32), B, C, T, H, W, T0, pt0, pt1, ph, pw)
+        wg = _WeightGrads()
+        dw0, dw1 = wg.add(dT0, rows0, need["w0"]), wg.add(dT1, rows1, need["w1"])
+        wg.run()
+        sw0, sw1, sp0, sp1, slt = ctx.shapes
+        return _grads(ctx, DualPatchEmbed, video=dvideo, w0=dw0.reshape(sw0) if dw0 is not None else None, w1=dw1.reshape(sw1) if dw1 is not None else None,
+                      b0=hip.colsum(dT0, rows=B * n0) if need["b0"] else None, b1=hip.colsum(dT1, rows=B * n1) if need["b1"] else None,
+                      pos0=hip.batch_sum(d2, B, n0, rmap=m0).reshape(sp0) if need["pos0"] else None,
+                      pos1=hip.batch_sum(d2, B, n1, rmap=m1).reshape(sp1) if need["pos1"] else None,
+                      lead_table=hip.batch_sum(d2, B, lead, rmap=hip.RowMap(lead, L, 0)).reshape(slt) if need["lead_table"] else None)
+
+
+class DualConvTransposePatch(torch.autograd.Function):
+    """Decoder.forward behind the layer stack (blocks.py:234-257): rows [lead, lead + N0) of every sequence of `stream` fp32 [B, L, D] through
+    ConvTranspose3d(D, C, kernel = stride = (pt0, ph, pw)) into frames [0, T0), the N1 rows behind them through ConvTranspose3d((pt1, ph, pw))
+    into frames [T0, T): vt_cast_rows per segment through a row map, two GEMMs into patch rows (c, dt, dy, dx) rounded to bf16 like the convs
+    under autocast, ONE vt_unpatchify_dual (no torch.cat of two videos).  geom = (B, C, T, H, W, T0, pt0, pt1, ph, pw).
+    Backward: ONE vt_patchify_dual of d video (bf16 rows, as titok.ConvTransposePatch), two input-gradient GEMMs written into d stream through
+    the row maps, vt_zero_rows for the lead rows (nothing reads the stack's latent rows), grouped weight gradients, vt_colsum for the biases."""
+
+    @staticmethod
+    def forward(ctx, stream, lead, w0, b0, w1, b1, geom):
+        hip.require_gpu(stream, w0, b0, w1, b1)
+        B, C, T, H, W, T0, pt0, pt1, ph, pw = geom
+        D = w0.shape[0]
+        n0, n1 = hip.dual_grids(T, H, W, T0, pt0, pt1, ph, pw)
+        L = lead + n0 + n1
+        assert stream.shape == (B, L, D) and w0.shape == (D, C, pt0, ph, pw) and w1.shape == (D, C, pt1, ph, pw)
+        s2 = stream.contiguous().float().view(B * L, D)
+        m0, m1 = _dual_maps(lead, n0, n1, L)
+        x0, x1 = hip.cast_rows(s2, rows=B * n0, rmap=m0), hip.cast_rows(s2, rows=B * n1, rmap=m1)
+        wb0, wt0 = hip.pack_weight(w0.reshape(D, -1).t().contiguous())       # B operand [Kp, D]; wt = [D, Kp]
+        wb1, wt1 = hip.pack_weight(w1.reshape(D, -1).t().contiguous())
+        r0 = hip.gemm_nt(x0, wb0, hip.EPI_F32, bias=b0.detach().float().repeat_interleave(pt0 * ph * pw).contiguous(), round_bf16=True)
+        r1 = hip.gemm_nt(x1, wb1, hip.EPI_F32, bias=b1.detach().float().repeat_interleave(pt1 * ph * pw).contiguous(), round_bf16=True)
+        ctx.save_for_backward(x0, x1, wt0, wt1)
+        ctx.geom, ctx.lead = geom, lead
+        return hip.unpatchify_dual(r0, r1, B, C, T, H, W, T0, pt0, pt1, ph, pw)
+
+    @staticmethod
+    def backward(ctx, dvideo):
+        x0, x1, wt0, wt1 = ctx.saved_tensors
+        B, C, T, H, W, T0, pt0, pt1, ph, pw = ctx.geom
+        lead, D = ctx.lead, x0.shape[1]
+        n0, n1 = hip.dual_grids(T, H, W, T0, pt0, pt1, ph, pw)
+        L = lead + n0 + n1
+        need = _needs(ctx, DualConvTransposePatch)
+        dr0, dr1 = hip.patchify_dual(dvideo.contiguous().float(), T0, pt0, pt1, ph, pw)      # bf16 [B * N, Kp]
+        dstream = None
+        if need["stream"]:
+            dstream = torch.empty(B, L, D, device=dvideo.device)
+            d2 = dstream.view(B * L, D)
+            m0, m1 = _dual_maps(lead, n0, n1, L)
+            hip.gemm_nt(dr0, wt0, hip.EPI_F32, round_bf16=True, omap=m0, out=d2)
+            hip.gemm_nt(dr1, wt1, hip.EPI_F32, round_bf16=True, omap=m1, out=d2)
+            if lead:
+                hip.zero_rows(d2, rows=B * lead, rmap=hip.RowMap(lead, L, 0))
+        wg = _WeightGrads()
+        dw0, dw1 = wg.add(x0, dr0, need["w0"]), wg.add(x1, dr1, need["w1"])
+        wg.run()
+        return _grads(ctx, DualConvTransposePatch, stream=dstream, w0=dw0.reshape(D, C, pt0, ph, pw) if dw0 is not None else None,
+                      w1=dw1.reshape(D, C, pt1, ph, pw) if dw1 is not None else None,
+                      b0=hip.colsum(dr0, rows=B * n0).reshape(C, -1).sum(dim=1) if need["b0"] else None,
+                      b1=hip.colsum(dr1, rows=B * n1).reshape(C, -1).sum(dim=1) if need["b1"] else None)
+
+
+class DualDecoderStream(torch.autograd.Function):
+    """The decoder's sequence (blocks.py:222-229): [x + latent_pos | first_patch_queries | rest_patch_queries] as fp32 [B, n + N0 + N1, D] by three
+    vt_assemble_rows calls (x: the proj_in output fp32 [B, n, D]; the tables [1, rows, D], broadcast over the batch), no torch.cat.
+    Backward: d x is the first n rows of every sequence, the tables' gradients are vt_batch_sum through a row map."""
+
+    @staticmethod
+    def forward(ctx, x, latent_pos, q0, q1):
+        hip.require_gpu(x, latent_pos, q0, q1)
+        B, n, D = x.shape
+        n0, n1 = q0.numel() // D, q1.numel() // D
+        L = n + n0 + n1
+        assert latent_pos.numel() == n * D
+        out = torch.empty(B, L, D, device=x.device)
+        o2 = out.view(B * L, D)
+        tab = [t.detach().reshape(-1, D).float().contiguous() for t in (latent_pos, q0, q1)]
+        hip.assemble_rows(o2, L, 0, B, n, src=x.contiguous().float().view(B * n, D), table=tab[0])
+        hip.assemble_rows(o2, L, n, B, n0, table=tab[1])
+        hip.assemble_rows(o2, L, n + n0, B, n1, table=tab[2])
+        ctx.geom = (B, n, n0, n1, D)
+        ctx.shapes = (latent_pos.shape, q0.shape, q1.shape)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        B, n, n0, n1, D = ctx.geom
+        L = n + n0 + n1
+        need = _needs(ctx, DualDecoderStream)
+        d = dout.contiguous().float()
+        d2 = d.view(B * L, D)
+        s_lp, s_q0, s_q1 = ctx.shapes
+        return _grads(ctx, DualDecoderStream, x=d[:, :n],
+                      latent_pos=hip.batch_sum(d2, B, n, rmap=hip.RowMap(n, L, 0)).reshape(s_lp) if need["latent_pos"] else None,
+                      q0=hip.batch_sum(d2, B, n0, rmap=hip.RowMap(n0, L, n)).reshape(s_q0) if need["q0"] else None,
+                      q1=hip.batch_sum(d2, B, n1, rmap=hip.RowMap(n1, L, n + n0)).reshape(s_q1) if need["q1"] else None)

@@ -66,6 +66,8 @@ SIGNATURES = {
     "vt_pack_weight": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp]),
     "vt_patchify": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "vt_unpatchify": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    "vt_patchify_dual": (c_i32, [c_vp] + [c_i32] * 10 + [c_vp, c_vp, c_vp]),
+    "vt_unpatchify_dual": (c_i32, [c_vp, c_vp] + [c_i32] * 10 + [c_vp, c_vp]),
     "vt_attention_fwd": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "vt_attention_bwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "vt_attention_causal_fwd": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
@@ -468,6 +470,33 @@ def patchify(video, pt, p):
 def unpatchify(rows, B, C, T, S, pt, p):
     video = torch.empty(B, C, T, S, S, device=rows.device, dtype=torch.float32)
     check(lib().vt_unpatchify(ptr(rows), B, C, T, S, pt, p, ptr(video), stream()), "vt_unpatchify")
+    return video
+
+
+def dual_grids(T, H, W, T0, pt0, pt1, ph, pw):
+    """tokens per clip of the two temporal segments of vt_patchify_dual: (N0, N1)"""
+    return (T0 // pt0) * (H // ph) * (W // pw), ((T - T0) // pt1) * (H // ph) * (W // pw)
+
+
+def patchify_dual(video, T0, pt0, pt1, ph, pw, rows0=None, rows1=None):
+    """video fp32 [B, C, T, H, W] -> (rows0 bf16 [B * N0, C pt0 ph pw], rows1 bf16 [B * N1, C pt1 ph pw]): frames [0, T0) and [T0, T), one launch"""
+    B, C, T, H, W = video.shape
+    n0, n1 = dual_grids(T, H, W, T0, pt0, pt1, ph, pw)
+    rows0 = torch.empty(B * n0, C * pt0 * ph * pw, device=video.device, dtype=torch.bfloat16) if rows0 is None else rows0
+    rows1 = torch.empty(B * n1, C * pt1 * ph * pw, device=video.device, dtype=torch.bfloat16) if rows1 is None else rows1
+    assert video.dtype == torch.float32 and video.is_contiguous() and rows0.dtype == torch.bfloat16 == rows1.dtype
+    assert rows0.numel() >= B * n0 * C * pt0 * ph * pw and rows1.numel() >= B * n1 * C * pt1 * ph * pw
+    check(lib().vt_patchify_dual(ptr(video), B, C, T, H, W, T0, pt0, pt1, ph, pw, ptr(rows0), ptr(rows1), stream()), "vt_patchify_dual")
+    return rows0, rows1
+
+
+def unpatchify_dual(rows0, rows1, B, C, T, H, W, T0, pt0, pt1, ph, pw, video=None):
+    """the inverse on two fp32 row matrices -> video fp32 [B, C, T, H, W], one launch"""
+    video = torch.empty(B, C, T, H, W, device=rows0.device, dtype=torch.float32) if video is None else video
+    n0, n1 = dual_grids(T, H, W, T0, pt0, pt1, ph, pw)
+    assert rows0.dtype == torch.float32 == rows1.dtype == video.dtype and video.numel() >= B * C * T * H * W
+    assert rows0.numel() >= B * n0 * C * pt0 * ph * pw and rows1.numel() >= B * n1 * C * pt1 * ph * pw
+    check(lib().vt_unpatchify_dual(ptr(rows0), ptr(rows1), B, C, T, H, W, T0, pt0, pt1, ph, pw, ptr(video), stream()), "vt_unpatchify_dual")
     return video
 
 
