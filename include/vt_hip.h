@@ -211,6 +211,53 @@ int vt_unpatchify_dual(const float* rows0, const float* rows1, int32_t B, int32_
                        int32_t pt1, int32_t ph, int32_t pw, float* video, vtStream stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The 3D ResNet ends of `autoencoder_cnnvit` (models/model_cnnvit/base/cnnvit.py): 3x3x3 convolution with padding 1, GroupNorm with an
+ * optional swish, nearest-neighbour upsampling, and the video layout pair.  Activations are bf16 channels-last [B, T, H, W, C] (the memory
+ * of a torch [B, C, T, H, W] tensor in channels_last_3d); channel counts are multiples of 16 up to 1024 (the 3-channel video ends are
+ * zero-padded to 16 by the layout pair and the weight pack).  Strides (st, sh, sw) are (1,1,1), (1,2,2) or (2,2,2); T, H, W are always the
+ * extents of the convolution's INPUT, its output has ((n - 1) / s + 1) per axis.  Everything is checked on the host before any launch
+ * (VT_ERR_INVALID, vt_last_error names the entry point and the value); no atomics; every sum has a fixed order, so a second call gives the
+ * same bits.
+ *
+ * vt_conv3d_pack_weight: the fp32 parameter [Cout, Cin, 3, 3, 3] -> the bf16 operand image of the forward (for_dgrad 0) or of the input
+ *   gradient (for_dgrad 1: transposed, taps mirrored), vt_conv3d_packed_elems(n_abi, k_abi) bf16 elements (n, k = cout_abi, cin_abi forward and
+ *   cin_abi, cout_abi for dgrad); rows / columns past Cout / Cin are zero.
+ * vt_conv3d_fwd: out = bf16(acc + bias); with `residual` (same shape as out, may be null) out = bf16(float(bf16(acc + bias)) + float(res)).
+ * vt_conv3d_dgrad: dx bf16 [B, T, H, W, Cin] from dy bf16 [B, T', H', W', Cout], fp32 sum.
+ * vt_conv3d_wgrad: dw fp32 [cout_lim, cin_lim, 3, 3, 3] (the leading part of the channel ranges: the parameter's own extents at a padded
+ *   end), summed over all B T' H' W' output positions; `workspace` holds vt_conv3d_wgrad_workspace_bytes(...) of fp32 partials.
+ * ------------------------------------------------------------------------------------------ */
+size_t vt_conv3d_packed_elems(int32_t n_abi, int32_t k_abi);
+int vt_conv3d_pack_weight(const float* w, int32_t Cout, int32_t Cin, int32_t cout_abi, int32_t cin_abi, int32_t for_dgrad, void* packed_bf16,
+                          vtStream stream);
+int vt_conv3d_fwd(const void* x_bf16, const void* w_packed, const float* bias, const void* residual_bf16, int32_t B, int32_t T, int32_t H, int32_t W,
+                  int32_t Cin, int32_t Cout, int32_t st, int32_t sh, int32_t sw, void* out_bf16, vtStream stream);
+int vt_conv3d_dgrad(const void* dy_bf16, const void* w_packed_dgrad, int32_t B, int32_t T, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t st,
+                    int32_t sh, int32_t sw, void* dx_bf16, vtStream stream);
+size_t vt_conv3d_wgrad_workspace_bytes(int32_t B, int32_t T, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t st, int32_t sh, int32_t sw,
+                                       int32_t cout_lim, int32_t cin_lim);
+int vt_conv3d_wgrad(const void* x_bf16, const void* dy_bf16, int32_t B, int32_t T, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t st, int32_t sh,
+                    int32_t sw, int32_t cout_lim, int32_t cin_lim, float* dw, void* workspace, vtStream stream);
+/* GroupNorm(G, C, eps) over (C/G channels x P positions) of each clip of x bf16 [B, P, C]; swish 1: z = y sigmoid(y).  Statistics in fp32 from
+ * the bf16 input, variance as the mean of squared deviations from the mean; y rounded to bf16 once; mean / rstd fp32 [B, G].  The backward
+ * takes the forward's input, mean and rstd and gives dx bf16 and dgamma / dbeta fp32 [C].  One workspace size serves both. */
+size_t vt_groupnorm_workspace_bytes(int32_t B, int64_t P, int32_t C, int32_t G);
+int vt_groupnorm_fwd(const void* x_bf16, const float* gamma, const float* beta, float eps, int32_t B, int64_t P, int32_t C, int32_t G, int32_t swish,
+                     void* y_bf16, float* mean, float* rstd, void* workspace, vtStream stream);
+int vt_groupnorm_bwd(const void* dz_bf16, const void* x_bf16, const float* gamma, const float* beta, const float* mean, const float* rstd, int32_t B,
+                     int64_t P, int32_t C, int32_t G, int32_t swish, void* dx_bf16, float* dgamma, float* dbeta, void* workspace, vtStream stream);
+/* nearest-neighbour upsampling by (ft, fh, fw) = (2,2,2) or (1,2,2), src = dst / f; T, H, W are the SOURCE extents.  The backward adds the 4 or 8
+ * children of a source position in fp32, in (t, h, w) order, and rounds once. */
+int vt_upsample_nearest_fwd(const void* x_bf16, int32_t B, int32_t T, int32_t H, int32_t W, int32_t C, int32_t ft, int32_t fh, int32_t fw, void* out_bf16,
+                            vtStream stream);
+int vt_upsample_nearest_bwd(const void* dout_bf16, int32_t B, int32_t T, int32_t H, int32_t W, int32_t C, int32_t ft, int32_t fh, int32_t fw, void* dx_bf16,
+                            vtStream stream);
+/* fp32 video [B, C, T, H, W] -> bf16 channels-last [B, T, H, W, Cpad] with channels C .. Cpad - 1 zero, and back (fp32 holding the bf16 values;
+ * the pad channels are not read) */
+int vt_video_to_channels_last(const float* video, int32_t B, int32_t C, int32_t T, int32_t H, int32_t W, int32_t Cpad, void* out_bf16, vtStream stream);
+int vt_channels_last_to_video(const void* x_bf16, int32_t B, int32_t C, int32_t T, int32_t H, int32_t W, int32_t Cpad, float* video, vtStream stream);
+
+/* ------------------------------------------------------------------------------------------
  * Fused attention, head_dim 64, no mask (timm Attention -> F.scaled_dot_product_attention inside
  * timm Block, models/transformer.py:52-59).  qkv bf16 [B,L,3,H,64]; o/dO bf16 [B,L,H,64];
  * lse2 fp32 [B,H,L] (log2-domain LSE of the scaled scores, saved for backward);

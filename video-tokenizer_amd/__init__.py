@@ -43,6 +43,8 @@ from . import titok_model  # noqa: F401  (registers 'titok')
 from .titok_model import TiTok  # noqa: F401
 from . import dualpatch  # noqa: F401  (registers 'autoencoder_dualpatch')
 from .dualpatch import AutoEncoderDualPatch, DualPatchDecoder, DualPatchEncoder  # noqa: F401
+from . import cnnvit  # noqa: F401  (the 3D ResNet ends of autoencoder_cnnvit; the model itself is not registered yet)
+from .cnnvit import AttnBlock3D, Decoder_cnn, Downsample3D, Encoder_cnn, ResnetBlock3D, Upsample3D  # noqa: F401
 from .design import (AutoEncoder, CrossAttention, Encoder, FirstFrameEncoder, LearnedQueryTokens, RMSNorm, SelfAttention,  # noqa: F401
                      TransformerBlock, TransformerStack, UnifiedDecoder)
 

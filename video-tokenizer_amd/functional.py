@@ -21,6 +21,10 @@ PackedGather); varlen.py and titok_model.py hold their parameters.
 
 Last come the ends of `autoencoder_dualpatch` (DualPatchEmbed, DualConvTransposePatch, DualDecoderStream: a clip cut along time into two segments
 with a patch size each, csrc/vt_dualpatch.hip); dualpatch.py holds their parameters.
+
+The 3D ResNet ends of `autoencoder_cnnvit` close the file (Conv3x3x3, GroupNormSwish, UpsampleNearest, VideoToChannelsLast, ChannelsLastToVideo:
+csrc/vt_conv3d.hip, vt_groupnorm.hip); cnnvit.py holds their parameters.  They take and return logical [B, C, T, H, W] bf16 tensors whose
+memory is channels-last ([B, T, H, W, C], torch.channels_last_3d), which is what the kernels read.
 """
 import ctypes
 import functools
@@ -29,7 +33,7 @@ import operator
 
 import torch
 
-from . import hip
+from . import hip, packs
 
 
 def _pad64(m):
@@ -1105,3 +1109,122 @@ class DualDecoderStream(torch.autograd.Function):
                       latent_pos=hip.batch_sum(d2, B, n, rmap=hip.RowMap(n, L, 0)).reshape(s_lp) if need["latent_pos"] else None,
                       q0=hip.batch_sum(d2, B, n0, rmap=hip.RowMap(n0, L, n)).reshape(s_q0) if need["q0"] else None,
                       q1=hip.batch_sum(d2, B, n1, rmap=hip.RowMap(n1, L, n + n0)).reshape(s_q1) if need["q1"] else None)
+
+
+# ---- the 3D ResNet ends of autoencoder_cnnvit -------------------------------------------------------------------------------------------------
+def _pad16(c):
+    return (c + 15) // 16 * 16
+
+
+def _cl(x):
+    """logical [B, C, T, H, W] -> the bf16 [B, T, H, W, C] the kernels read: a view where x is bf16 channels_last_3d already, one copy otherwise"""
+    if x is None:
+        return None
+    assert x.dim() == 5
+    return x.to(torch.bfloat16).permute(0, 2, 3, 4, 1).contiguous()
+
+
+def _logical(x_cl):
+    """bf16 [B, T, H, W, C] -> the logical [B, C, T, H, W] view of the same memory (channels_last_3d)"""
+    return x_cl.permute(0, 4, 1, 2, 3)
+
+
+class Conv3x3x3(torch.autograd.Function):
+    """nn.Conv3d(kernel 3, padding 1, stride (1,1,1) / (1,2,2) / (2,2,2)) under autocast(bf16) on channels-last activations (cnnvit.py:21-28,
+    86, 95, 115, 172): out = bf16(acc + bias), and with `residual` bf16(float(bf16(acc + bias)) + float(residual)), the two roundings autocast gives
+    `x + conv2(h)`.  `owner`, `name`: the module and attribute path of the nn.Conv3d, for the pack registry.  A 3-channel end runs at 16 channels:
+    the input's pad channels are zero (VideoToChannelsLast), the output's are bf16(0 + 0)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, residual, stride, owner, name):
+        hip.require_gpu(x, weight, bias, residual)
+        xc = _cl(x)
+        cout, cin = weight.shape[:2]
+        cout_abi, cin_abi = _pad16(cout), xc.shape[-1]
+        assert cin_abi == _pad16(cin), f"Conv3x3x3: the input has {xc.shape[-1]} channels, the weight {cin}"
+        b = bias.detach().float()
+        if cout_abi != cout:
+            b = torch.nn.functional.pad(b, (0, cout_abi - cout))
+        out = hip.conv3d_fwd(xc, packs.conv3d(owner, name, cout_abi, cin_abi), b.contiguous(), cout_abi, stride, residual=_cl(residual))
+        ctx.save_for_backward(xc)
+        ctx.conv = (stride, owner, name, cout, cin, cout_abi, cin_abi)
+        return _logical(out)
+
+    @staticmethod
+    def backward(ctx, dy):
+        xc, = ctx.saved_tensors
+        stride, owner, name, cout, cin, cout_abi, cin_abi = ctx.conv
+        need = _needs(ctx, Conv3x3x3)
+        dyc = _cl(dy)                                               # the gradient of a bf16 output is bf16 under autocast
+        dx = dw = db = None
+        if need["x"]:
+            dx = _logical(hip.conv3d_dgrad(dyc, packs.conv3d(owner, name, cout_abi, cin_abi, for_dgrad=True), tuple(xc.shape[1:4]), cin_abi, stride))
+        if need["weight"]:
+            dw = hip.conv3d_wgrad(xc, dyc, stride, cout, cin)
+        if need["bias"]:
+            db = hip.colsum(dyc.view(-1, cout_abi))[:cout].contiguous()
+        return _grads(ctx, Conv3x3x3, x=dx, weight=dw, bias=db, residual=dy)
+
+
+class GroupNormSwish(torch.autograd.Function):
+    """nn.GroupNorm(G, C, eps) and, with swish, x * sigmoid(x) behind it (cnnvit.py:5-10): statistics and the activation in fp32 from the bf16
+    input, rounded to bf16 once."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, groups, eps, swish):
+        hip.require_gpu(x, weight, bias)
+        xc = _cl(x)
+        w, b = weight.detach().float().contiguous(), bias.detach().float().contiguous()
+        y, mean, rstd = hip.groupnorm_fwd(xc, w, b, eps, groups, swish)
+        ctx.save_for_backward(xc, w, b, mean, rstd)
+        ctx.gn = (groups, swish)
+        return _logical(y)
+
+    @staticmethod
+    def backward(ctx, dy):
+        xc, w, b, mean, rstd = ctx.saved_tensors
+        dx, dg, db = hip.groupnorm_bwd(_cl(dy), xc, w, b, mean, rstd, *ctx.gn)
+        return _grads(ctx, GroupNormSwish, x=_logical(dx), weight=dg, bias=db)
+
+
+class UpsampleNearest(torch.autograd.Function):
+    """F.interpolate(x, scale_factor=(2,2,2) or (1,2,2), mode='nearest') (cnnvit.py:99); the backward adds a position's children in fp32"""
+
+    @staticmethod
+    def forward(ctx, x, scale):
+        hip.require_gpu(x)
+        ctx.scale = tuple(int(s) for s in scale)
+        return _logical(hip.upsample_nearest_fwd(_cl(x), ctx.scale))
+
+    @staticmethod
+    def backward(ctx, dy):
+        return _logical(hip.upsample_nearest_bwd(_cl(dy), ctx.scale)), None
+
+
+class VideoToChannelsLast(torch.autograd.Function):
+    """fp32 video [B, C, T, H, W] -> the logical [B, 16k, T, H, W] bf16 channels-last activation, channels C.. zero (the autocast cast in front
+    of conv_in); the video's gradient is computed only when the video requires one"""
+
+    @staticmethod
+    def forward(ctx, video):
+        hip.require_gpu(video)
+        ctx.C = video.shape[1]
+        return _logical(hip.video_to_channels_last(video.float().contiguous(), _pad16(ctx.C)))
+
+    @staticmethod
+    def backward(ctx, dy):
+        return hip.channels_last_to_video(_cl(dy), ctx.C)
+
+
+class ChannelsLastToVideo(torch.autograd.Function):
+    """the first C channels of a logical [B, 16k, T, H, W] bf16 activation -> fp32 [B, C, T, H, W] holding the bf16 values (as pred_frames elsewhere)"""
+
+    @staticmethod
+    def forward(ctx, x, C):
+        hip.require_gpu(x)
+        ctx.cpad = x.shape[1]
+        return hip.channels_last_to_video(_cl(x), C)
+
+    @staticmethod
+    def backward(ctx, dvideo):
+        return _logical(hip.video_to_channels_last(dvideo.float().contiguous(), ctx.cpad)), None

@@ -68,6 +68,19 @@ SIGNATURES = {
     "vt_unpatchify": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "vt_patchify_dual": (c_i32, [c_vp] + [c_i32] * 10 + [c_vp, c_vp, c_vp]),
     "vt_unpatchify_dual": (c_i32, [c_vp, c_vp] + [c_i32] * 10 + [c_vp, c_vp]),
+    "vt_conv3d_packed_elems": (c_sz, [c_i32, c_i32]),
+    "vt_conv3d_pack_weight": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    "vt_conv3d_fwd": (c_i32, [c_vp, c_vp, c_vp, c_vp] + [c_i32] * 9 + [c_vp, c_vp]),
+    "vt_conv3d_dgrad": (c_i32, [c_vp, c_vp] + [c_i32] * 9 + [c_vp, c_vp]),
+    "vt_conv3d_wgrad_workspace_bytes": (c_sz, [c_i32] * 11),
+    "vt_conv3d_wgrad": (c_i32, [c_vp, c_vp] + [c_i32] * 11 + [c_vp, c_vp, c_vp]),
+    "vt_groupnorm_workspace_bytes": (c_sz, [c_i32, c_i64, c_i32, c_i32]),
+    "vt_groupnorm_fwd": (c_i32, [c_vp, c_vp, c_vp, c_f32, c_i32, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "vt_groupnorm_bwd": (c_i32, [c_vp] * 6 + [c_i32, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "vt_upsample_nearest_fwd": (c_i32, [c_vp] + [c_i32] * 8 + [c_vp, c_vp]),
+    "vt_upsample_nearest_bwd": (c_i32, [c_vp] + [c_i32] * 8 + [c_vp, c_vp]),
+    "vt_video_to_channels_last": (c_i32, [c_vp] + [c_i32] * 6 + [c_vp, c_vp]),
+    "vt_channels_last_to_video": (c_i32, [c_vp] + [c_i32] * 6 + [c_vp, c_vp]),
     "vt_attention_fwd": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "vt_attention_bwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "vt_attention_causal_fwd": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
@@ -1218,3 +1231,116 @@ def rmsnorm_any_f32_bwd(dy, x, w, rstd):
     assert dy.dtype == torch.float32 and dy.is_contiguous() and tuple(dy.shape) == tuple(x.shape)
     dx, _, dw = _rmsnorm_bwd("vt_rmsnorm_any_f32", dy, x, w, rstd)
     return dx, dw
+
+
+# ---- the 3D ResNet ends of autoencoder_cnnvit (csrc/vt_conv3d.hip, vt_groupnorm.hip): activations bf16 channels-last [B, T, H, W, C] ----------
+def conv3d_out_dims(T, H, W, stride):
+    return tuple((n - 1) // s + 1 for n, s in zip((T, H, W), stride))
+
+
+def conv3d_pack_weight(w, cout_abi, cin_abi, for_dgrad=False):
+    """fp32 [Cout, Cin, 3, 3, 3] -> the bf16 operand image of vt_conv3d_fwd (or of vt_conv3d_dgrad), channel counts padded to the ABI's"""
+    require_gpu(w)
+    assert w.dtype == torch.float32 and w.is_contiguous() and w.shape[2:] == (3, 3, 3)
+    n, k = (cin_abi, cout_abi) if for_dgrad else (cout_abi, cin_abi)
+    packed = torch.empty(lib().vt_conv3d_packed_elems(n, k), device=w.device, dtype=torch.bfloat16)
+    check(lib().vt_conv3d_pack_weight(ptr(w), w.shape[0], w.shape[1], cout_abi, cin_abi, int(for_dgrad), ptr(packed), stream()), "vt_conv3d_pack_weight")
+    return packed
+
+
+def _cl_dims(x):
+    assert x.dtype == torch.bfloat16 and x.dim() == 5 and x.is_contiguous()
+    return x.shape
+
+
+def conv3d_fwd(x, w_packed, bias, cout, stride=(1, 1, 1), residual=None, out=None):
+    """x bf16 [B, T, H, W, Cin] -> bf16 [B, T', H', W', cout]; bias fp32 [cout]; residual bf16 like the output"""
+    B, T, H, W, Cin = _cl_dims(x)
+    To, Ho, Wo = conv3d_out_dims(T, H, W, stride)
+    out = torch.empty(B, To, Ho, Wo, cout, device=x.device, dtype=torch.bfloat16) if out is None else out
+    assert bias.dtype == torch.float32 and bias.numel() == cout and out.numel() >= B * To * Ho * Wo * cout
+    assert residual is None or (residual.dtype == torch.bfloat16 and residual.numel() >= B * To * Ho * Wo * cout)
+    check(lib().vt_conv3d_fwd(ptr(x), ptr(w_packed), ptr(bias), ptr(residual), B, T, H, W, Cin, cout, *stride, ptr(out), stream()), "vt_conv3d_fwd")
+    return out
+
+
+def conv3d_dgrad(dy, w_packed_dgrad, in_dims, cin, stride=(1, 1, 1), dx=None):
+    """dy bf16 [B, T', H', W', Cout] -> dx bf16 [B, T, H, W, cin]; in_dims = (T, H, W) of the convolution's input"""
+    B, To, Ho, Wo, Cout = _cl_dims(dy)
+    T, H, W = in_dims
+    assert (To, Ho, Wo) == conv3d_out_dims(T, H, W, stride)
+    dx = torch.empty(B, T, H, W, cin, device=dy.device, dtype=torch.bfloat16) if dx is None else dx
+    assert dx.numel() >= B * T * H * W * cin
+    check(lib().vt_conv3d_dgrad(ptr(dy), ptr(w_packed_dgrad), B, T, H, W, cin, Cout, *stride, ptr(dx), stream()), "vt_conv3d_dgrad")
+    return dx
+
+
+def conv3d_wgrad(x, dy, stride=(1, 1, 1), cout_lim=None, cin_lim=None, dw=None):
+    """dW fp32 [cout_lim, cin_lim, 3, 3, 3] from x bf16 [B, T, H, W, Cin] and dy bf16 [B, T', H', W', Cout]"""
+    B, T, H, W, Cin = _cl_dims(x)
+    Cout = _cl_dims(dy)[-1]
+    assert tuple(dy.shape[:4]) == (B,) + conv3d_out_dims(T, H, W, stride)
+    cout_lim, cin_lim = cout_lim or Cout, cin_lim or Cin
+    dw = torch.empty(cout_lim, cin_lim, 3, 3, 3, device=x.device, dtype=torch.float32) if dw is None else dw
+    ws = _ws(lib().vt_conv3d_wgrad_workspace_bytes(B, T, H, W, Cin, Cout, *stride, cout_lim, cin_lim), x.device)
+    check(lib().vt_conv3d_wgrad(ptr(x), ptr(dy), B, T, H, W, Cin, Cout, *stride, cout_lim, cin_lim, ptr(dw), ptr(ws), stream()), "vt_conv3d_wgrad")
+    return dw
+
+
+def groupnorm_fwd(x, gamma, beta, eps, G, swish, y=None):
+    """x bf16 [B, ..., C] channels-last -> (y bf16 like x, mean fp32 [B, G], rstd fp32 [B, G])"""
+    assert x.dtype == torch.bfloat16 and x.is_contiguous()
+    B, C = x.shape[0], x.shape[-1]
+    P = x.numel() // (B * C)
+    y = torch.empty_like(x) if y is None else y
+    mean, rstd = torch.empty(B, G, device=x.device), torch.empty(B, G, device=x.device)
+    ws = _ws(lib().vt_groupnorm_workspace_bytes(B, P, C, G), x.device)
+    check(lib().vt_groupnorm_fwd(ptr(x), ptr(gamma), ptr(beta), eps, B, P, C, G, int(swish), ptr(y), ptr(mean), ptr(rstd), ptr(ws), stream()),
+          "vt_groupnorm_fwd")
+    return y, mean, rstd
+
+
+def groupnorm_bwd(dz, x, gamma, beta, mean, rstd, G, swish, dx=None):
+    """-> (dx bf16 like x, dgamma fp32 [C], dbeta fp32 [C])"""
+    assert x.dtype == torch.bfloat16 == dz.dtype and x.is_contiguous() and dz.is_contiguous()
+    B, C = x.shape[0], x.shape[-1]
+    P = x.numel() // (B * C)
+    dx = torch.empty_like(x) if dx is None else dx
+    dg, db = torch.empty(C, device=x.device), torch.empty(C, device=x.device)
+    ws = _ws(lib().vt_groupnorm_workspace_bytes(B, P, C, G), x.device)
+    check(lib().vt_groupnorm_bwd(ptr(dz), ptr(x), ptr(gamma), ptr(beta), ptr(mean), ptr(rstd), B, P, C, G, int(swish), ptr(dx), ptr(dg), ptr(db), ptr(ws),
+                                 stream()), "vt_groupnorm_bwd")
+    return dx, dg, db
+
+
+def upsample_nearest_fwd(x, scale, out=None):
+    B, T, H, W, C = _cl_dims(x)
+    out = torch.empty(B, T * scale[0], H * scale[1], W * scale[2], C, device=x.device, dtype=torch.bfloat16) if out is None else out
+    check(lib().vt_upsample_nearest_fwd(ptr(x), B, T, H, W, C, *scale, ptr(out), stream()), "vt_upsample_nearest_fwd")
+    return out
+
+
+def upsample_nearest_bwd(dout, scale, dx=None):
+    B, To, Ho, Wo, C = _cl_dims(dout)
+    T, H, W = To // scale[0], Ho // scale[1], Wo // scale[2]
+    assert (T * scale[0], H * scale[1], W * scale[2]) == (To, Ho, Wo)
+    dx = torch.empty(B, T, H, W, C, device=dout.device, dtype=torch.bfloat16) if dx is None else dx
+    check(lib().vt_upsample_nearest_bwd(ptr(dout), B, T, H, W, C, *scale, ptr(dx), stream()), "vt_upsample_nearest_bwd")
+    return dx
+
+
+def video_to_channels_last(video, cpad=16, out=None):
+    """fp32 [B, C, T, H, W] -> bf16 [B, T, H, W, cpad], channels C.. zero"""
+    assert video.dtype == torch.float32 and video.is_contiguous()
+    B, C, T, H, W = video.shape
+    out = torch.empty(B, T, H, W, cpad, device=video.device, dtype=torch.bfloat16) if out is None else out
+    check(lib().vt_video_to_channels_last(ptr(video), B, C, T, H, W, cpad, ptr(out), stream()), "vt_video_to_channels_last")
+    return out
+
+
+def channels_last_to_video(x, C, video=None):
+    """bf16 [B, T, H, W, cpad] -> fp32 [B, C, T, H, W] holding the bf16 values of the first C channels"""
+    B, T, H, W, cpad = _cl_dims(x)
+    video = torch.empty(B, C, T, H, W, device=x.device, dtype=torch.float32) if video is None else video
+    check(lib().vt_channels_last_to_video(ptr(x), B, C, T, H, W, cpad, ptr(video), stream()), "vt_channels_last_to_video")
+    return video

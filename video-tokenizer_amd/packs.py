@@ -77,3 +77,18 @@ def invalidate(module):
         if rec is not None:
             rec.epoch += 1
             rec.entries.clear()
+
+
+def conv3d(owner, name, cout_abi, cin_abi, for_dgrad=False):
+    """The operand image of the 3x3x3 convolution `name` of `owner` (an attribute path to an nn.Conv3d: "conv1", "downsample.conv") for
+    vt_conv3d_fwd, or for vt_conv3d_dgrad (transposed, taps mirrored); channel counts zero-padded to the ABI's.  Cached like `get`."""
+    rec = _owner(owner)
+    w = operator.attrgetter(name)(owner).weight
+    key = (rec.epoch,) + _versions([w])
+    slot = ("conv3d", name, cout_abi, cin_abi, bool(for_dgrad))
+    hit = rec.entries.get(slot)
+    if hit is None or hit[0] != key:
+        with torch.no_grad():
+            pack = hip.conv3d_pack_weight(w.detach().float().contiguous(), cout_abi, cin_abi, for_dgrad)
+        hit = rec.entries[slot] = (key, pack)
+    return hit[1]
