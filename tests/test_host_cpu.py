@@ -345,6 +345,30 @@ def test_gemm_nt_rejects_the_removed_tile_values():
         assert b"tile %d" % tile in buf.value, buf.value
 
 
+def test_layernorm_and_pack_refusals_keep_their_code_and_text():
+    """The refusals of vt_layernorm_* and vt_pack_weight* come from the host-side validation (no launch, no GPU): an unsupported width, a
+    leading dimension below the extent, a null source, a bad job in a group (named by its index).  Each gives -1 and this exact message."""
+    lib = vt.hip.lib()
+    P, ident = 4096, vt.hip.IDENT              # P: non-null, 16-byte aligned, never dereferenced
+    jobs = (vt.hip.PackJob * 2)()
+    for j in jobs:
+        j.w, j.N, j.K, j.wb, j.ldd, j.lddT = P, 64, 64, P, 64, 64
+    jobs[1].w = None
+    widths = b"dim=192 must be 128, 256, 384, 512, 768 or 1024"
+    cases = [
+        (lambda: lib.vt_layernorm_fwd(P, ident, P, P, 1e-5, 8, 192, P, P, P, None), b"vt_layernorm_fwd: " + widths),
+        (lambda: lib.vt_layernorm_bwd(P, P, ident, P, P, P, None, 8, 192, P, None, P, P, None, P, None), b"vt_layernorm_bwd: " + widths),
+        (lambda: lib.vt_pack_weight(P, 64, 64, None, P, 63, None, 0, None), b"vt_pack_weight: leading dimension too small"),
+        (lambda: lib.vt_pack_weight(None, 64, 64, None, P, 64, None, 0, None), b"vt_pack_weight: bad arguments"),
+        (lambda: lib.vt_pack_weights_grouped(jobs, 2, None), b"vt_pack_weights_grouped[1]: bad arguments"),
+    ]
+    buf = ctypes.create_string_buffer(512)
+    for call, text in cases:
+        assert call() == -1, text
+        lib.vt_last_error(buf, 512)
+        assert buf.value == text
+
+
 def test_engine_plan_sizes_host_only():
     """vt_tokenizer_create / workspace_bytes are pure host planning: config B at 8 clips/GPU fits easily in 288 GB."""
     lib = vt.hip.lib()

@@ -1,4 +1,4 @@
-"""The row kernels of csrc/vt_norm.hip (and vt_scale_rows) at the sizes where they take another path: the grid-stride loops (LayerNorm
+"""The row kernels of csrc/vt_layernorm.hip and csrc/vt_rows.hip at the sizes where they take another path: the grid-stride loops (LayerNorm
 forward rows > 8192, backward rows > 2048), the 32-lane partial reduction (>= 128 slabs, i.e. rows >= 509), a last workgroup with idle
 waves, every supported width, row maps, every optional operand absent in turn, the 64-slab cap and the 4 x 4-row unrolled loop of
 vt_colsum, element counts that cross a 256-thread block.  References are float64 torch on the same inputs.

@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libvt_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-SOURCES = ["vt_api.cpp", "vt_gemm.hip", "vt_gemm192.hip", "vt_norm.hip", "vt_patch.hip", "vt_vq.hip", "vt_attention.hip", "vt_optim.hip", "vt_fsq.hip", "vt_gated.hip", "vt_stat.hip", "vt_kl.hip", "vt_rope.hip", "vt_ar.hip", "vt_rmsnorm.hip", "vt_cross.hip", "vt_design.hip", "vt_varlen.hip", "vt_packed.hip", "vt_dualpatch.hip", "vt_engine.hip", "vt_gated_engine.hip", "vt_conv3d.hip", "vt_groupnorm.hip"]
+SOURCES = ["vt_api.cpp", "vt_gemm.hip", "vt_gemm192.hip", "vt_layernorm.hip", "vt_rows.hip", "vt_pack.hip", "vt_patch.hip", "vt_vq.hip", "vt_attention.hip", "vt_optim.hip", "vt_fsq.hip", "vt_gated.hip", "vt_stat.hip", "vt_kl.hip", "vt_rope.hip", "vt_ar.hip", "vt_rmsnorm.hip", "vt_cross.hip", "vt_design.hip", "vt_varlen.hip", "vt_packed.hip", "vt_dualpatch.hip", "vt_engine.hip", "vt_gated_engine.hip", "vt_conv3d.hip", "vt_groupnorm.hip"]
 AUDIT_NO_SPILL = {"vt_gemm.hip", "vt_gemm192.hip", "vt_attention.hip", "vt_stat.hip", "vt_rope.hip", "vt_rmsnorm.hip", "vt_cross.hip", "vt_design.hip", "vt_varlen.hip", "vt_packed.hip", "vt_dualpatch.hip", "vt_conv3d.hip", "vt_groupnorm.hip"}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 

@@ -235,6 +235,7 @@ struct RowMap {
         return grp ? (r / grp) * stride + off + (r % grp) : r;
     }
 };
+static inline RowMap to_map(vtRowMap m) { return RowMap{m.grp, m.stride, m.off}; }
 
 // ---- library-private (not part of the C ABI): deferred partial-sum reductions of the tokenizer engine ----------------------
 // The backward of a block leaves three sets of per-slab partial sums (fc1 bias gradient out of the gelu' epilogue, the two
@@ -252,6 +253,9 @@ int vt_reduce_grouped(const vtReduceItem* items, int n, vtStream stream);
 // dst[t / 64][t % 64] (up to four destinations of 64 elements, fewer elements if nout says so; a null destination is skipped).  One wave per
 // element: lane l adds partials l, l + 64, ... in order, then wave_sum.  `who` names the launch in a failure's message.
 int vt_reduce_waves(const char* who, const float* part, int nblk, int64_t row_stride, int nout, float* d0, float* d1, float* d2, float* d3, vtStream stream);
+// The stand-alone reducer of per-slab partial sums: o_w[c] = sum_s partial[s * slab_stride + w * width + c] for the one to three destinations
+// given (o1, o2 may be null: the destinations are o0, or o0 and o1).  32 slab lanes per column from 128 slabs on, 8 below; `who` as above.
+int vt_reduce_partials(const char* who, const float* partial, int nslab, int64_t slab_stride, int width, float* o0, float* o1, float* o2, vtStream stream);
 // LayerNorm backward without its reduction: partial sums go to `part` ([grid][3 * dim]); *nslab = grid
 int vt_layernorm_bwd_partials(const void* dy_bf16, const float* x, vtRowMap xmap, const float* gamma, const float* mean, const float* rstd,
                               const float* dres, int64_t rows, int32_t dim, float* dx, void* dx_bf16, float* part, int* nslab, vtStream stream);

@@ -2,7 +2,7 @@
 // /root/reference/models/model_new/base/transformer.py:66-91 (Attn :32-63, ffd :20-29) and its backward as ONE enqueue per
 // direction.  Replaces the Python composition of round 1 (~50 launches per layer and direction issued from Python, host-bound
 // at the `small` model size; now the tests' bit-exact reference, tests/gated_layer_reference.py).  Nothing here allocates or synchronises: a sequence of launches of the
-// kernels in vt_gemm*.hip, vt_gated.hip, vt_attention.hip, vt_norm.hip on the caller's stream, over one caller-owned workspace.
+// kernels in vt_gemm*.hip, vt_gated.hip, vt_attention.hip, vt_layernorm.hip, vt_rows.hip on the caller's stream, over one caller-owned workspace.
 #include <math.h>
 
 #include <vector>
