@@ -187,7 +187,9 @@ int vt_pack_weights_grouped(const vtPackJob* jobs_host, int32_t n_jobs, vtStream
  * (T,H,W) patchify / unpatchify.  Patch-row columns are in (c,dt,dy,dx) order == Conv3d weight
  * flattening (models/embed.py:82,110-112); unpatchify is the inverse and, with the head weight
  * rows permuted at pack time, replaces LARPTokenizer.unpatchify's einops permute + .contiguous()
- * (models/larp_tokenizer.py:441-454,493).  p % 8 == 0.
+ * (models/larp_tokenizer.py:441-454,493).  p % 8 == 0.  The one-segment case of the kernel of csrc/vt_patch.hip (the lane layout, the
+ * patch map and the rounding are csrc/vt_patch_map.h, shared with the _dual and _clips entry points), validated like vt_patchify_dual
+ * below: VT_ERR_INVALID for a null or misaligned pointer, a size <= 0, T % pt, S % p, p % 8; S and p are reported as H = W and ph = pw.
  * ------------------------------------------------------------------------------------------ */
 int vt_patchify(const float* video, int32_t B, int32_t C, int32_t T, int32_t S, int32_t pt, int32_t p, void* rows_bf16,
                 vtStream stream);
@@ -195,7 +197,7 @@ int vt_unpatchify(const float* rows, int32_t B, int32_t C, int32_t T, int32_t S,
                   vtStream stream);
 
 /* ------------------------------------------------------------------------------------------
- * Two-segment patchify / unpatchify (csrc/vt_dualpatch.hip): the ends of `autoencoder_dualpatch`.  Its encoder cuts the clip along time,
+ * Two-segment patchify / unpatchify (csrc/vt_patch.hip): the ends of `autoencoder_dualpatch`.  Its encoder cuts the clip along time,
  * x[:, :, :pt_first] into Conv3d(kernel = stride = (pt_first, ph, pw)) and x[:, :, pt_first:] into Conv3d((pt_rest, ph, pw))
  * (models/model_dualpatch/base/blocks.py:99-112); its decoder ends in two ConvTranspose3d whose outputs are concatenated along T
  * (blocks.py:252-257).  video fp32 [B, C, T, H, W] contiguous; frames [0, T0) <-> rows0 [B (T0/pt0)(H/ph)(W/pw), C pt0 ph pw], frames

@@ -1,4 +1,4 @@
-"""vt_patchify_dual / vt_unpatchify_dual (csrc/vt_dualpatch.hip) on the GPU.  The kernels only move data (patchify rounds once to bf16), so
+"""vt_patchify_dual / vt_unpatchify_dual (csrc/vt_patch.hip) on the GPU.  The kernels only move data (patchify rounds once to bf16), so
 equality is exact: against an einops.rearrange restatement of Conv3d patch extraction per temporal segment (kernel = stride = (pt, ph, pw),
 weight flattening (c, dt, dy, dx), token order (t, h, w)), against vt_patchify / vt_unpatchify on contiguous slices of square clips, and
 against their own inverse.

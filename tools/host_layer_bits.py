@@ -6,7 +6,8 @@ Legs: a `tiny` gated FSQ autoencoder (8x32x32 clips, 32 tokens); a tiny `autoenc
 step; greedy generation of `class_S2` at the three VT_AR_FUSED_DECODE levels; a 2-block BlockStack, plain and rotary.  For the layer Functions'
 weight-gradient queue (functional._WeightGrads): `varlen.Attn` on a ragged packed batch (M = 130); a tiny `autoencoder_stat` step; Bottleneck
 and PatchEmbed3D on their own at M = 72; one design block with cross attention, all trainable, with cross_attn.to_gate frozen and with
-self_attn.to_qkv frozen; the `class_S2` step with one w1 frozen.
+self_attn.to_qkv frozen; the `class_S2` step with one w1 frozen.  For the patch ends (csrc/vt_patch.hip, vt_packed.hip and their Functions): a tiny
+`autoencoder_dualpatch` step and a small packed `titok` step on two clips of different sizes.
 
   python tools/host_layer_bits.py > listing.txt
   python tools/host_layer_bits.py --flat-order > order.txt      (no GPU: engine._flat_order of configs `tiny` and `B`)
@@ -205,6 +206,31 @@ def ar_training_w1_frozen():
     report("ar_train_class_S2_w1_frozen", logits, m, extra=[("loss", loss)])
 
 
+def dualpatch_autoencoder():
+    """a tiny `autoencoder_dualpatch` step (case A of tests/dualpatch_reference.py: 7 frames of 32 x 64, a one-frame first segment): DualPatchEmbed
+    and DualConvTransposePatch, both weight gradients of each in one grouped launch"""
+    from tests import dualpatch_reference as D
+    c = D.CASES["A"]
+    torch.manual_seed(16)
+    m = vt.make({"name": "autoencoder_dualpatch", "args": {"bottleneck": None, "prior_model": None, "_geometry": dict(
+        dims=c["dims"], tokens=c["tokens"], **D.geometry("A"))}}).cuda()
+    step("dualpatch_ae", m, lambda v: m(v)["pred_frames"], [torch.from_numpy(D.video("A")).cuda()], normal(D.video_shape("A"), 1951))
+
+
+def titok_packed():
+    """a small packed `titok` step on two clips of different sizes through encode / decode: PatchRowsClips and UnpatchifyClips"""
+    from tests import titok_reference as K
+    torch.manual_seed(17)
+    m = vt.TiTok(_geometry=dict(dims=K.CASES["A"]["dims"])).cuda()
+    sizes, counts = [(4, 16, 16), (8, 16, 24)], [24, 40]
+    ups = [normal((3,) + s, 1962 + i) for i, s in enumerate(sizes)]
+
+    def run(*clips):
+        x_q, _ = m.encode(list(clips), counts)
+        return torch.cat([(p * u).reshape(-1) for p, u in zip(m.decode(x_q, counts, sizes), ups)])
+    step("titok_packed", m, run, [torch.from_numpy(gen.uniform((3,) + s, 1960 + i)).cuda() for i, s in enumerate(sizes)], 1.0)
+
+
 def flat_order():
     """--flat-order (no GPU needed): (stage, name) of engine._flat_order, the layout of the flat gradient buffer and of the all-reduce slices"""
     from video_tokenizer_amd.engine import _flat_order
@@ -229,3 +255,5 @@ if __name__ == "__main__":
     ragged_projections()
     design_blocks_half_frozen()
     ar_training_w1_frozen()
+    dualpatch_autoencoder()
+    titok_packed()

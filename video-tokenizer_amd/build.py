@@ -11,8 +11,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libvt_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-SOURCES = ["vt_api.cpp", "vt_gemm.hip", "vt_gemm192.hip", "vt_layernorm.hip", "vt_rows.hip", "vt_pack.hip", "vt_patch.hip", "vt_vq.hip", "vt_attention.hip", "vt_optim.hip", "vt_fsq.hip", "vt_gated.hip", "vt_stat.hip", "vt_kl.hip", "vt_rope.hip", "vt_ar.hip", "vt_rmsnorm.hip", "vt_cross.hip", "vt_design.hip", "vt_varlen.hip", "vt_packed.hip", "vt_dualpatch.hip", "vt_engine.hip", "vt_gated_engine.hip", "vt_conv3d.hip", "vt_groupnorm.hip"]
-AUDIT_NO_SPILL = {"vt_gemm.hip", "vt_gemm192.hip", "vt_attention.hip", "vt_stat.hip", "vt_rope.hip", "vt_rmsnorm.hip", "vt_cross.hip", "vt_design.hip", "vt_varlen.hip", "vt_packed.hip", "vt_dualpatch.hip", "vt_conv3d.hip", "vt_groupnorm.hip"}
+SOURCES = ["vt_api.cpp", "vt_gemm.hip", "vt_gemm192.hip", "vt_layernorm.hip", "vt_rows.hip", "vt_pack.hip", "vt_patch.hip", "vt_vq.hip", "vt_attention.hip", "vt_optim.hip", "vt_fsq.hip", "vt_gated.hip", "vt_stat.hip", "vt_kl.hip", "vt_rope.hip", "vt_ar.hip", "vt_rmsnorm.hip", "vt_cross.hip", "vt_design.hip", "vt_varlen.hip", "vt_packed.hip", "vt_engine.hip", "vt_gated_engine.hip", "vt_conv3d.hip", "vt_groupnorm.hip"]
+AUDIT_NO_SPILL = {"vt_gemm.hip", "vt_gemm192.hip", "vt_attention.hip", "vt_stat.hip", "vt_rope.hip", "vt_rmsnorm.hip", "vt_cross.hip", "vt_design.hip", "vt_varlen.hip", "vt_packed.hip", "vt_patch.hip", "vt_conv3d.hip", "vt_groupnorm.hip"}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 
 
@@ -51,7 +51,7 @@ def build(force=False, verbose=False):
             # asm destination before its data has landed (silent wrong results), so spills are a build error
             # (SGPR spills go to VGPR lanes by v_writelane, no memory involved: allowed)
             # vt_stat.hip has no inline asm; it is audited because its row passes keep per-lane column arrays in registers by
-            # construction, and scratch there would be a silent regression; vt_rope.hip, vt_cross.hip, vt_design.hip and vt_varlen.hip likewise (a lane's 8 elements and 8 factors / weights), and vt_rmsnorm.hip (a lane's pieces of a whole row); vt_packed.hip takes its tables in the kernel arguments, and scratch would mean a table was copied per lane; vt_dualpatch.hip likewise takes its two-segment geometry in the kernel arguments and picks a segment by select, not by indexing; vt_conv3d.hip reads its transposed LDS operands through the ds_read_tr builtin and keeps 27 tap accumulators in registers by construction, and vt_groupnorm.hip a lane's 8 channels and their statistics
+            # construction, and scratch there would be a silent regression; vt_rope.hip, vt_cross.hip, vt_design.hip and vt_varlen.hip likewise (a lane's 8 elements and 8 factors / weights), and vt_rmsnorm.hip (a lane's pieces of a whole row); vt_packed.hip takes its tables in the kernel arguments, and scratch would mean a table was copied per lane; vt_patch.hip likewise takes its one- or two-segment geometry in the kernel arguments and picks a segment by select, not by indexing; vt_conv3d.hip reads its transposed LDS operands through the ds_read_tr builtin and keeps 27 tap accumulators in registers by construction, and vt_groupnorm.hip a lane's 8 channels and their statistics
             bad = [ln for ln in text.splitlines() if ("VGPRs Spill:" in ln or "ScratchSize" in ln)
                    and not ln.rstrip().endswith(" 0 [-Rpass-analysis=kernel-resource-usage]")]
             if bad:

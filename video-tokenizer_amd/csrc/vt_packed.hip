@@ -17,7 +17,7 @@
 //                   other segment takes vec[D] (or zeros): blocks.py:132-135 and :197-200, and the backward of the gather.
 // packed_gather   : the chosen segment's rows of a packed [M, D] -> compact (blocks.py:140-142, :207-209).
 // packed_segment_colsum: out[D] = sum over the chosen segment's rows of all sequences (the gradient of mask_token), in a fixed order.
-#include "vt_common.h"
+#include "vt_patch_map.h"
 
 namespace {
 
@@ -43,38 +43,18 @@ __device__ __forceinline__ int find_entry(const int* __restrict__ start, int n, 
     return __builtin_amdgcn_readfirstlane(lo);
 }
 
-// Threads are laid out over the VIDEO index space of one clip, so the video side is fully coalesced (unit idx = pixels 8 idx .. 8 idx + 7
-// of the contiguous clip); the patch-row side moves 16-B (bf16) / 32-B (fp32) pieces.
+// A workgroup works on one clip (found by bisection, so every table index is wave-uniform); behind that the lane layout, the patch map and the
+// move are those of vt_patch_map.h, with the clip as the whole contiguous block (its plane is the channel).
 template <bool TO_ROWS>
 __global__ __launch_bounds__(256) void clips_kernel(const ClipTable tab, void* __restrict__ rows_) {
     const int b = find_entry(tab.blk0, tab.n, blockIdx.x);
     const int T = tab.T[b], H = tab.H[b], W = tab.W[b];
-    const int w8 = W >> 3;
-    const int64_t units = (int64_t)tab.C * T * H * w8;
+    const int64_t units = (int64_t)tab.C * T * H * (W >> 3);
     const int64_t idx = (int64_t)(blockIdx.x - tab.blk0[b]) * 256 + threadIdx.x;
     if (idx >= units) return;
-    int64_t r = idx;
-    const int x = (int)(r % w8) * 8;
-    r /= w8;
-    const int y = (int)(r % H);
-    r /= H;
-    const int t = (int)(r % T);
-    const int c = (int)(r / T);
-    const int Hh = H / tab.p, Ww = W / tab.p;
-    const int tt = t / tab.pt, dt = t % tab.pt, hh = y / tab.p, dy = y % tab.p, ww = x / tab.p, dx = x % tab.p;
-    const int64_t tok = (int64_t)tab.row0[b] + ((int64_t)tt * Hh + hh) * Ww + ww;
-    const int col = ((c * tab.pt + dt) * tab.p + dy) * tab.p + dx;
-    const int64_t off = tok * tab.Kp + col;
-    float* vid = (float*)tab.ptr[b] + idx * 8;
-    if constexpr (TO_ROWS) {
-        const f32x4 a0 = *(const f32x4*)vid, a1 = *(const f32x4*)(vid + 4);
-        const bf16x8 o = {f2bf(a0[0]), f2bf(a0[1]), f2bf(a0[2]), f2bf(a0[3]), f2bf(a1[0]), f2bf(a1[1]), f2bf(a1[2]), f2bf(a1[3])};
-        *(bf16x8*)((bf16_t*)rows_ + off) = o;
-    } else {
-        const float* src = (const float*)rows_ + off;
-        *(f32x4*)vid = *(const f32x4*)src;
-        *(f32x4*)(vid + 4) = *(const f32x4*)(src + 4);
-    }
+    const PatchUnit u = patch_unit(idx, T, H, W);
+    const int64_t off = patch_offset((int)u.plane, u.t, u.y, u.x, tab.pt, tab.Kp, tab.p, tab.p, H / tab.p, W / tab.p, tab.row0[b]);
+    patch_move<TO_ROWS>((float*)tab.ptr[b] + idx * 8, rows_, off);
 }
 
 int clip_table(const char* who, const vtClip* clips, int n, int C, int pt, int p, int64_t rows_total, ClipTable* tab) {

@@ -8,7 +8,7 @@ Same module tree and state-dict keys as the reference (`encoder.first_patch_embe
 `decoder.latent_pos_embed`, `decoder.first_patch_queries`, `decoder.rest_patch_queries`, `decoder.model_layers.*`, `decoder.first_unpatch`,
 `decoder.rest_unpatch`; `quantize` has no entries), the same constructor keywords and defaults, the same init.
 
-The ends run on csrc/vt_dualpatch.hip (functional.DualPatchEmbed / DualConvTransposePatch / DualDecoderStream): one patchify launch for both
+The ends run on the two-segment entry points of csrc/vt_patch.hip (functional.DualPatchEmbed / DualConvTransposePatch / DualDecoderStream): one patchify launch for both
 segments, GEMMs that write straight into the residual stream, one unpatchify launch for both segments.  The layer stack is the gated
 LayerNorm-per-head stack of titok.ResidualAttentionBlock (base/transformer.py:58-81 of this family is that stack WITHOUT a rotary embedding)
 with identity rotary tables: cos = 1, sin = 0 changes no value (x * 1 + y * (+-0) == x), so no second instantiation of the qk-norm kernel

@@ -20,7 +20,7 @@ and VarlenFeedForwardLayer (one Function per half block), and the data movement 
 PackedGather); varlen.py and titok_model.py hold their parameters.
 
 Last come the ends of `autoencoder_dualpatch` (DualPatchEmbed, DualConvTransposePatch, DualDecoderStream: a clip cut along time into two segments
-with a patch size each, csrc/vt_dualpatch.hip); dualpatch.py holds their parameters.
+with a patch size each, the two-segment entry points of csrc/vt_patch.hip); dualpatch.py holds their parameters.
 
 The 3D ResNet ends of `autoencoder_cnnvit` close the file (Conv3x3x3, GroupNormSwish, UpsampleNearest, VideoToChannelsLast, ChannelsLastToVideo:
 csrc/vt_conv3d.hip, vt_groupnorm.hip); cnnvit.py holds their parameters.  They take and return logical [B, C, T, H, W] bf16 tensors whose
@@ -293,6 +293,45 @@ class GatedStack(torch.autograd.Function):
         return (dx, None, None, None, None, *[g if n else None for g, n in zip(grads, need)])
 
 
+# The patch ends: a Conv3d / ConvTranspose3d with kernel = stride = (pt, ph, pw) is a patch gather / scatter (csrc/vt_patch.hip) and one GEMM
+# per temporal segment.  The per-segment pieces below are shared by PatchEmbed, ConvTransposePatch (one segment) and their Dual siblings (two);
+# each Function keeps the order of its own library calls.
+def _f32(t):
+    return None if t is None else t.detach().float().contiguous()
+
+
+def _conv_tokens(patches, wb, bias, pos, n, **into):
+    """Conv3d forward of one segment: bf16 patch rows [B * n, Kp] x the packed weight -> tokens fp32 [B * n, D], rounded to bf16 like the conv
+    under autocast, then + pos [n, D] (or None) in fp32 in the epilogue; into = omap=, out= to write the rows into a stream"""
+    kw = dict(rowmod=_f32(pos.reshape(n, -1)), rowmod_period=n) if pos is not None else {}
+    return hip.gemm_nt(patches, wb, hip.EPI_F32, bias=_f32(bias), round_bf16=True, **kw, **into)
+
+
+def _convt_weight(weight):
+    """ConvTranspose3d weight [D, C, pt, ph, pw] packed as the B operand [Kp, D] of the forward; -> (wb, wt = [D, Kp])"""
+    return hip.pack_weight(weight.reshape(weight.shape[0], -1).t().contiguous())
+
+
+def _convt_rows(x, wb, bias, taps):
+    """ConvTranspose3d forward of one segment: bf16 tokens [M, D] -> patch rows fp32 [M, Kp] in (c, dt, dy, dx) order, each channel's bias on its
+    taps = pt * ph * pw columns, rounded to bf16 like the conv under autocast"""
+    return hip.gemm_nt(x, wb, hip.EPI_F32, bias=_f32(bias).repeat_interleave(taps).contiguous(), round_bf16=True)
+
+
+def _convt_input_grad(drows, wt, **into):
+    """d tokens [M, D] of one segment from the bf16 patch rows of d video, a bf16 gradient under autocast; into = omap=, out="""
+    return hip.gemm_nt(drows, wt, hip.EPI_F32, round_bf16=True, **into)
+
+
+def _convt_bias_grad(drows, C):
+    """d bias [C] of one segment: the column sums of the patch rows of d video, summed over each channel's taps"""
+    return hip.colsum(drows, rows=drows.shape[0]).reshape(C, -1).sum(dim=1)
+
+
+def _shaped(dw, shape):
+    return None if dw is None else dw.reshape(shape)
+
+
 class PatchEmbed(torch.autograd.Function):
     """PatchEmbed3D.forward (models/embed.py:85-116): Conv3d(kernel = stride = (pt,p,p)) as patch gather + one GEMM,
     bf16-rounded like the conv under autocast, then (optionally) + pos_embed [N, D] in fp32, fused in the epilogue."""
@@ -304,10 +343,9 @@ class PatchEmbed(torch.autograd.Function):
         B = video.shape[0]
         video = video.contiguous().float()
         patches = hip.patchify(video, pt, p)                       # [B*N, Kp] bf16, (c,dt,dy,dx) inside a patch
-        M, Kp = patches.shape
+        M = patches.shape[0]
         wb, wt = hip.pack_weight(weight)
-        kw = dict(rowmod=pos_embed.reshape(-1, D).contiguous(), rowmod_period=M // B) if pos_embed is not None else {}
-        tok = hip.gemm_nt(patches, wb, hip.EPI_F32, bias=bias, round_bf16=True, **kw)
+        tok = _conv_tokens(patches, wb, bias, pos_embed, M // B)
         ctx.save_for_backward(patches, wt)
         ctx.geom = (B, C, video.shape[2], video.shape[3], pt, p, D)
         return tok.reshape(B, M // B, D)
@@ -495,6 +533,40 @@ class Unpatchify(torch.autograd.Function):
     def backward(ctx, dvideo):
         B, C, T, S, pt, p = ctx.geom
         return hip.patchify(dvideo.contiguous().float(), pt, p).float(), None
+
+
+class ConvTransposePatch(torch.autograd.Function):
+    """nn.ConvTranspose3d(width, C, kernel = stride = (pt, p, p)) on a token grid (blocks.py:116-147): one GEMM into patch
+    rows (c, dt, dy, dx) + the LARP path's unpatchify scatter; bf16-rounded output like the conv under autocast."""
+
+    @staticmethod
+    def forward(ctx, tok, weight, bias, geom):
+        hip.require_gpu(tok, weight, bias)
+        B, C, T, S, pt, p = geom
+        width = weight.shape[0]
+        M = tok.shape[0] * tok.shape[1]
+        if M % 64:
+            raise hip.HipError("ConvTransposePatch: B * tokens must be a multiple of 64")
+        xb = hip.cast_rows(tok.contiguous().reshape(M, width).float())
+        wb, wt = _convt_weight(weight)
+        rows = _convt_rows(xb, wb, bias, pt * p * p)
+        ctx.save_for_backward(xb, wt)
+        ctx.geom = geom
+        return hip.unpatchify(rows, B, C, T, S, pt, p)
+
+    @staticmethod
+    def backward(ctx, dvideo):
+        xb, wt = ctx.saved_tensors
+        B, C, T, S, pt, p = ctx.geom
+        need = _needs(ctx, ConvTransposePatch)
+        drows = hip.patchify(dvideo.contiguous().float(), pt, p)              # bf16 [M, Kp], (c, dt, dy, dx) inside a patch
+        M, width = xb.shape
+        dtok = _convt_input_grad(drows, wt)                                    # [M, width]
+        wg = _WeightGrads()
+        dw = wg.add(xb, drows, need["weight"])
+        wg.run()
+        return _grads(ctx, ConvTransposePatch, tok=dtok.reshape(B, M // B, width), weight=_shaped(dw, (width, C, pt, p, p)),
+                      bias=_convt_bias_grad(drows, C))
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -987,11 +1059,9 @@ class DualPatchEmbed(torch.autograd.Function):
         out = torch.empty(B, L, D, device=video.device)
         o2 = out.view(B * L, D)
         m0, m1 = _dual_maps(lead, n0, n1, L)
-        hip.gemm_nt(rows0, wb0, hip.EPI_F32, bias=b0.detach().float().contiguous(), round_bf16=True, rowmod=pos0.detach().reshape(n0, D).float().contiguous(),
-                    rowmod_period=n0, omap=m0, out=o2)
-        hip.gemm_nt(rows1, wb1, hip.EPI_F32, bias=b1.detach().float().contiguous(), round_bf16=True, rowmod=pos1.detach().reshape(n1, D).float().contiguous(),
-                    rowmod_period=n1, omap=m1, out=o2)
-        hip.assemble_rows(o2, L, 0, B, lead, table=lead_table.detach().reshape(lead, D).float().contiguous())
+        _conv_tokens(rows0, wb0, b0, pos0, n0, omap=m0, out=o2)
+        _conv_tokens(rows1, wb1, b1, pos1, n1, omap=m1, out=o2)
+        hip.assemble_rows(o2, L, 0, B, lead, table=_f32(lead_table.reshape(lead, D)))
         ctx.save_for_backward(rows0, rows1, wt0, wt1)
         ctx.geom = (B, C, T, H, W, T0, pt0, pt1, ph, pw, D, lead, n0, n1)
         ctx.shapes = (w0.shape, w1.shape, pos0.shape, pos1.shape, lead_table.shape)
@@ -1014,7 +1084,7 @@ class DualPatchEmbed(torch.autograd.Function):
         dw0, dw1 = wg.add(dT0, rows0, need["w0"]), wg.add(dT1, rows1, need["w1"])
         wg.run()
         sw0, sw1, sp0, sp1, slt = ctx.shapes
-        return _grads(ctx, DualPatchEmbed, video=dvideo, w0=dw0.reshape(sw0) if dw0 is not None else None, w1=dw1.reshape(sw1) if dw1 is not None else None,
+        return _grads(ctx, DualPatchEmbed, video=dvideo, w0=_shaped(dw0, sw0), w1=_shaped(dw1, sw1),
                       b0=hip.colsum(dT0, rows=B * n0) if need["b0"] else None, b1=hip.colsum(dT1, rows=B * n1) if need["b1"] else None,
                       pos0=hip.batch_sum(d2, B, n0, rmap=m0).reshape(sp0) if need["pos0"] else None,
                       pos1=hip.batch_sum(d2, B, n1, rmap=m1).reshape(sp1) if need["pos1"] else None,
@@ -1026,7 +1096,7 @@ class DualConvTransposePatch(torch.autograd.Function):
     ConvTranspose3d(D, C, kernel = stride = (pt0, ph, pw)) into frames [0, T0), the N1 rows behind them through ConvTranspose3d((pt1, ph, pw))
     into frames [T0, T): vt_cast_rows per segment through a row map, two GEMMs into patch rows (c, dt, dy, dx) rounded to bf16 like the convs
     under autocast, ONE vt_unpatchify_dual (no torch.cat of two videos).  geom = (B, C, T, H, W, T0, pt0, pt1, ph, pw).
-    Backward: ONE vt_patchify_dual of d video (bf16 rows, as titok.ConvTransposePatch), two input-gradient GEMMs written into d stream through
+    Backward: ONE vt_patchify_dual of d video (bf16 rows, as ConvTransposePatch), two input-gradient GEMMs written into d stream through
     the row maps, vt_zero_rows for the lead rows (nothing reads the stack's latent rows), grouped weight gradients, vt_colsum for the biases."""
 
     @staticmethod
@@ -1040,10 +1110,8 @@ class DualConvTransposePatch(torch.autograd.Function):
         s2 = stream.contiguous().float().view(B * L, D)
         m0, m1 = _dual_maps(lead, n0, n1, L)
         x0, x1 = hip.cast_rows(s2, rows=B * n0, rmap=m0), hip.cast_rows(s2, rows=B * n1, rmap=m1)
-        wb0, wt0 = hip.pack_weight(w0.reshape(D, -1).t().contiguous())       # B operand [Kp, D]; wt = [D, Kp]
-        wb1, wt1 = hip.pack_weight(w1.reshape(D, -1).t().contiguous())
-        r0 = hip.gemm_nt(x0, wb0, hip.EPI_F32, bias=b0.detach().float().repeat_interleave(pt0 * ph * pw).contiguous(), round_bf16=True)
-        r1 = hip.gemm_nt(x1, wb1, hip.EPI_F32, bias=b1.detach().float().repeat_interleave(pt1 * ph * pw).contiguous(), round_bf16=True)
+        (wb0, wt0), (wb1, wt1) = _convt_weight(w0), _convt_weight(w1)
+        r0, r1 = _convt_rows(x0, wb0, b0, pt0 * ph * pw), _convt_rows(x1, wb1, b1, pt1 * ph * pw)
         ctx.save_for_backward(x0, x1, wt0, wt1)
         ctx.geom, ctx.lead = geom, lead
         return hip.unpatchify_dual(r0, r1, B, C, T, H, W, T0, pt0, pt1, ph, pw)
@@ -1062,17 +1130,15 @@ class DualConvTransposePatch(torch.autograd.Function):
             dstream = torch.empty(B, L, D, device=dvideo.device)
             d2 = dstream.view(B * L, D)
             m0, m1 = _dual_maps(lead, n0, n1, L)
-            hip.gemm_nt(dr0, wt0, hip.EPI_F32, round_bf16=True, omap=m0, out=d2)
-            hip.gemm_nt(dr1, wt1, hip.EPI_F32, round_bf16=True, omap=m1, out=d2)
+            _convt_input_grad(dr0, wt0, omap=m0, out=d2)
+            _convt_input_grad(dr1, wt1, omap=m1, out=d2)
             if lead:
                 hip.zero_rows(d2, rows=B * lead, rmap=hip.RowMap(lead, L, 0))
         wg = _WeightGrads()
         dw0, dw1 = wg.add(x0, dr0, need["w0"]), wg.add(x1, dr1, need["w1"])
         wg.run()
-        return _grads(ctx, DualConvTransposePatch, stream=dstream, w0=dw0.reshape(D, C, pt0, ph, pw) if dw0 is not None else None,
-                      w1=dw1.reshape(D, C, pt1, ph, pw) if dw1 is not None else None,
-                      b0=hip.colsum(dr0, rows=B * n0).reshape(C, -1).sum(dim=1) if need["b0"] else None,
-                      b1=hip.colsum(dr1, rows=B * n1).reshape(C, -1).sum(dim=1) if need["b1"] else None)
+        return _grads(ctx, DualConvTransposePatch, stream=dstream, w0=_shaped(dw0, (D, C, pt0, ph, pw)), w1=_shaped(dw1, (D, C, pt1, ph, pw)),
+                      b0=_convt_bias_grad(dr0, C) if need["b0"] else None, b1=_convt_bias_grad(dr1, C) if need["b1"] else None)
 
 
 class DualDecoderStream(torch.autograd.Function):

@@ -471,44 +471,52 @@ def pack_weight(w, row_perm=None, want_t=True, ldd=None, lddT=None, n_pad=None, 
     return wb, wt
 
 
-def patchify(video, pt, p):
-    B, C, T, S, _ = video.shape
-    kp = C * pt * p * p
-    nv = (T // pt) * (S // p) ** 2
-    rows = torch.empty(B * nv, kp, device=video.device, dtype=torch.bfloat16)
-    check(lib().vt_patchify(ptr(video), B, C, T, S, pt, p, ptr(rows), stream()), "vt_patchify")
-    return rows
-
-
-def unpatchify(rows, B, C, T, S, pt, p):
-    video = torch.empty(B, C, T, S, S, device=rows.device, dtype=torch.float32)
-    check(lib().vt_unpatchify(ptr(rows), B, C, T, S, pt, p, ptr(video), stream()), "vt_unpatchify")
-    return video
-
-
 def dual_grids(T, H, W, T0, pt0, pt1, ph, pw):
     """tokens per clip of the two temporal segments of vt_patchify_dual: (N0, N1)"""
     return (T0 // pt0) * (H // ph) * (W // pw), ((T - T0) // pt1) * (H // ph) * (W // pw)
 
 
+def _patch_ends(shape, pts, ph, pw, video, rows, rows_dtype):
+    """the shapes and allocations of the four dense patch wrappers: video fp32 [B, C, T, H, W] and, per temporal segment of `frames` frames and
+    temporal patch pt in pts = ((frames, pt), ...), a row matrix [B * (frames / pt)(H / ph)(W / pw), C pt ph pw] of rows_dtype.  What is None is
+    allocated, what is given must be contiguous, of that dtype and large enough; -> (video, rows)"""
+    B, C, T, H, W = shape
+    dev = (video if video is not None else rows[0]).device
+    sizes = [(B * (frames // pt) * (H // ph) * (W // pw), C * pt * ph * pw) for frames, pt in pts]
+    video = torch.empty(shape, device=dev, dtype=torch.float32) if video is None else video
+    rows = [torch.empty(size, device=dev, dtype=rows_dtype) if r is None else r for r, size in zip(rows, sizes)]
+    assert video.dtype == torch.float32 and video.is_contiguous() and video.numel() >= B * C * T * H * W
+    for r, (n, kp) in zip(rows, sizes):
+        assert r.dtype == rows_dtype and r.is_contiguous() and r.numel() >= n * kp
+    return video, rows
+
+
+def patchify(video, pt, p, rows=None):
+    """video fp32 [B, C, T, S, S] -> rows bf16 [B * (T / pt)(S / p)^2, C pt p p]"""
+    B, C, T, S, _ = video.shape
+    video, (rows,) = _patch_ends(video.shape, ((T, pt),), p, p, video, (rows,), torch.bfloat16)
+    check(lib().vt_patchify(ptr(video), B, C, T, S, pt, p, ptr(rows), stream()), "vt_patchify")
+    return rows
+
+
+def unpatchify(rows, B, C, T, S, pt, p, video=None):
+    """the inverse on an fp32 row matrix -> video fp32 [B, C, T, S, S]"""
+    video, (rows,) = _patch_ends((B, C, T, S, S), ((T, pt),), p, p, video, (rows,), torch.float32)
+    check(lib().vt_unpatchify(ptr(rows), B, C, T, S, pt, p, ptr(video), stream()), "vt_unpatchify")
+    return video
+
+
 def patchify_dual(video, T0, pt0, pt1, ph, pw, rows0=None, rows1=None):
     """video fp32 [B, C, T, H, W] -> (rows0 bf16 [B * N0, C pt0 ph pw], rows1 bf16 [B * N1, C pt1 ph pw]): frames [0, T0) and [T0, T), one launch"""
     B, C, T, H, W = video.shape
-    n0, n1 = dual_grids(T, H, W, T0, pt0, pt1, ph, pw)
-    rows0 = torch.empty(B * n0, C * pt0 * ph * pw, device=video.device, dtype=torch.bfloat16) if rows0 is None else rows0
-    rows1 = torch.empty(B * n1, C * pt1 * ph * pw, device=video.device, dtype=torch.bfloat16) if rows1 is None else rows1
-    assert video.dtype == torch.float32 and video.is_contiguous() and rows0.dtype == torch.bfloat16 == rows1.dtype
-    assert rows0.numel() >= B * n0 * C * pt0 * ph * pw and rows1.numel() >= B * n1 * C * pt1 * ph * pw
+    video, (rows0, rows1) = _patch_ends(video.shape, ((T0, pt0), (T - T0, pt1)), ph, pw, video, (rows0, rows1), torch.bfloat16)
     check(lib().vt_patchify_dual(ptr(video), B, C, T, H, W, T0, pt0, pt1, ph, pw, ptr(rows0), ptr(rows1), stream()), "vt_patchify_dual")
     return rows0, rows1
 
 
 def unpatchify_dual(rows0, rows1, B, C, T, H, W, T0, pt0, pt1, ph, pw, video=None):
     """the inverse on two fp32 row matrices -> video fp32 [B, C, T, H, W], one launch"""
-    video = torch.empty(B, C, T, H, W, device=rows0.device, dtype=torch.float32) if video is None else video
-    n0, n1 = dual_grids(T, H, W, T0, pt0, pt1, ph, pw)
-    assert rows0.dtype == torch.float32 == rows1.dtype == video.dtype and video.numel() >= B * C * T * H * W
-    assert rows0.numel() >= B * n0 * C * pt0 * ph * pw and rows1.numel() >= B * n1 * C * pt1 * ph * pw
+    video, (rows0, rows1) = _patch_ends((B, C, T, H, W), ((T0, pt0), (T - T0, pt1)), ph, pw, video, (rows0, rows1), torch.float32)
     check(lib().vt_unpatchify_dual(ptr(rows0), ptr(rows1), B, C, T, H, W, T0, pt0, pt1, ph, pw, ptr(video), stream()), "vt_unpatchify_dual")
     return video
 

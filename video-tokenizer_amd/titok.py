@@ -25,7 +25,7 @@ from torch import nn
 
 from . import hip, packs
 from .fsq import FSQ
-from .functional import GatedStack, LayerNormRows, Linear as LinearFn, PatchEmbed as PatchEmbedFn, _grads, _needs, _WeightGrads, gated_params, rotary_block_stack
+from .functional import ConvTransposePatch, GatedStack, LayerNormRows, Linear as LinearFn, PatchEmbed as PatchEmbedFn, gated_params, rotary_block_stack
 from .registry import register
 
 
@@ -104,44 +104,6 @@ def rope_positions_unify(cond_tokens, in_tokens, grid):
     p0 = rope_positions(cond_tokens, [1, grid[1], grid[2]])
     p1 = rope_positions(in_tokens, grid) + p0.max()
     return np.concatenate([p0[:cond_tokens], p1], axis=0)
-
-
-class ConvTransposePatch(torch.autograd.Function):
-    """nn.ConvTranspose3d(width, C, kernel = stride = (pt, p, p)) on a token grid (blocks.py:116-147): one GEMM into patch
-    rows (c, dt, dy, dx) + the LARP path's unpatchify scatter; bf16-rounded output like the conv under autocast."""
-
-    @staticmethod
-    def forward(ctx, tok, weight, bias, geom):
-        hip.require_gpu(tok, weight, bias)
-        B, C, T, S, pt, p = geom
-        width = weight.shape[0]
-        M = tok.shape[0] * tok.shape[1]
-        if M % 64:
-            raise hip.HipError("ConvTransposePatch: B * tokens must be a multiple of 64")
-        xb = hip.cast_rows(tok.contiguous().reshape(M, width).float())
-        w2 = weight.reshape(width, -1)                                         # [width, Kp]
-        wb, wt = hip.pack_weight(w2.t().contiguous())                          # B operand [Kp, width]; wt = [width, Kp]
-        rows = hip.gemm_nt(xb, wb, hip.EPI_F32, bias=bias.repeat_interleave(pt * p * p).contiguous(), round_bf16=True)
-        ctx.save_for_backward(xb, wt)
-        ctx.geom = geom
-        return hip.unpatchify(rows, B, C, T, S, pt, p)
-
-    @staticmethod
-    def backward(ctx, dvideo):
-        xb, wt = ctx.saved_tensors
-        B, C, T, S, pt, p = ctx.geom
-        need = _needs(ctx, ConvTransposePatch)
-        drows = hip.patchify(dvideo.contiguous().float(), pt, p)              # bf16 [M, Kp], (c, dt, dy, dx) inside a patch
-        M = drows.shape[0]
-        width = xb.shape[1]
-        dtok = hip.gemm_nt(drows, wt, hip.EPI_F32, round_bf16=True)            # [M, width]
-        wg = _WeightGrads()
-        dw = wg.add(xb, drows, need["weight"])
-        wg.run()
-        db = hip.colsum(drows, rows=M).reshape(C, pt * p * p).sum(dim=1)
-        if dw is not None:
-            dw = dw.reshape(width, C, pt, p, p)
-        return _grads(ctx, ConvTransposePatch, tok=dtok.reshape(B, M // B, width), weight=dw, bias=db)
 
 
 class GEGLU(nn.Module):
